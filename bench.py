@@ -1,21 +1,34 @@
 #!/usr/bin/env python3
 """Benchmark of the batched HoverAviary DYN path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--dump-outputs DIR] [--full]
 
 One "step" = one env.step() of every env (HoverAviary, cf2x, Physics.DYN, ActionType.RPM,
 240 Hz physics / 30 Hz control -> 8 substeps) on synthetic uniform [-1, 1] actions that are
 resident in HBM before the timed region.  Unit of work: one drone advanced one 1/240 s
 substep (drone*dt).  value = drone*dt of all ranks / max-over-ranks wall time of K steps.
 
-Multi-GPU: one process per GPU (torchrun); each rank owns E envs (weak scaling), there is no
-collective inside the timed loop.  The RCCL all-gather of the observation batch to a learner
-on rank 0 (config 5) is timed separately and reported under "handoff" (on one GPU: a one-rank RCCL
-group with the collectives forced).
+A plain run sets up, runs W warm-up steps, times exactly K steps in the chosen launch form
+(--mode), writes the last timed step's outputs if --dump-outputs is given, and prints the result
+line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  Everything else is behind
+--full.
 
-Extra JSON fields: "roofline" (step kernel, HIP events on the launch stream), "cpu_baseline"
-(the oracle, rank 0 at N=1), "parity" (the metric's state-L2 leg: GPU vs the C oracle over 5 s,
-beside the CPU baseline), "sweep" (large-N roofline), "kernel_us".
+--dump-outputs DIR: what a caller of the timed path holds after its last timed step, as
+DIR/<name>.npy (float32): obs, reward, terminated, truncated and terminal_obs (zero outside
+the envs that finished in that step).  The actions come from a seeded generator, so two runs with
+the same arguments see the same inputs.  Past 64 MB in all, a fixed seeded sample of the envs is
+written, with their indices in env_index.npy (float64).  Ranks above 0 write <name>_rank<r>.npy.
+
+Multi-GPU: one process per GPU (torchrun); each rank owns E envs (weak scaling), there is no
+collective inside the timed loop.
+
+--full adds, after the same headline line: the step kernel's duration by HIP events
+("kernel_us") and its "roofline", the eager and the other launch form's timings, the
+strong-scaling leg, the RCCL hand-off of the observation batch to a learner on rank 0 (config 5,
+"handoff"; on one GPU a one-rank RCCL group with the collectives forced), the latency model, the
+RL-rollout leg, "sweep" (large-N roofline), the other configs, "cpu_baseline" (the oracle, rank 0
+at N=1) and "parity" (the metric's state-L2 leg: GPU vs the C oracle over 5 s).  The --no-*
+options leave single legs out of a --full run.
 """
 import argparse
 import json
@@ -297,14 +310,15 @@ def _event_region_us(device, body, launches, min_launches=256):
     return 1000.0 * ev0.elapsed_time(ev1) / (reps * launches)
 
 
-def time_graph(sim, pool, steps, warmup, per_graph=256):
+def time_graph(sim, pool, steps, warmup, per_graph=256, kernel_time=True, after_timed=None):
     """Timed region in hipGraph mode: one graph = `per_graph` consecutive env.step() launches
     reading distinct pre-filled action slots, plus one graph of the remaining steps % per_graph
     launches, so that exactly `steps` steps are timed.  Before the timed region every captured
     graph is replayed at least once (the first replay of a graph pays its upload to the device),
     then `warmup` further untimed steps run, whatever `warmup` is.
     The kernel duration comes from _event_region_us over the same replays right after it (for
-    fewer than 256 steps: over one 256-launch graph of the same kind).
+    fewer than 256 steps: over one 256-launch graph of the same kind); None without `kernel_time`.
+    `after_timed()` runs right after the timed region, before anything else steps the sim.
     Returns (wall seconds, steps run, kernel us)."""
     P = pool.shape[0]
     steps = max(1, int(steps))
@@ -328,6 +342,10 @@ def time_graph(sim, pool, steps, warmup, per_graph=256):
         if tail is not None:
             tail.replay()
     wall = _timed_region(sim.device, body)
+    if after_timed is not None:
+        after_timed()
+    if not kernel_time:
+        return wall, steps, None
     if steps >= 256:
         return wall, steps, _event_region_us(sim.device, body, steps)
     # a short timed region: the kernel time from one 256-launch graph of the same steps, so that
@@ -340,7 +358,7 @@ def time_graph(sim, pool, steps, warmup, per_graph=256):
     return wall, steps, kern
 
 
-def time_native(sim, pool, steps, warmup):
+def time_native(sim, pool, steps, warmup, kernel_time=True, after_timed=None):
     """Timed region as ONE gpd_step_seq call: `steps` env.step() launches issued back to back from
     native code (step k reads action slot k % P), no graph.  Its per-region fixed cost is a little
     below a graph replay's, but each launch costs the host ~5-6 us (about one kernel), so at large
@@ -352,14 +370,17 @@ def time_native(sim, pool, steps, warmup):
     def body():
         sim.step_seq(pool, steps)
     wall = _timed_region(sim.device, body)
-    return wall, steps, _event_region_us(sim.device, body, steps)
+    if after_timed is not None:
+        after_timed()
+    return wall, steps, _event_region_us(sim.device, body, steps) if kernel_time else None
 
 
-def time_steps(sim, pool, steps, warmup):
+def time_steps(sim, pool, steps, warmup, kernel_time=True, after_timed=None):
     """Eager launches (one BatchedAviarySim.step() call per env.step, as an SB3-style caller
     makes them): the wall time of `steps` back-to-back calls, then a second pass with a HIP event
-    pair around every gpd_step on the launch stream for the per-launch kernel time.
-    Returns (wall seconds, mean kernel us)."""
+    pair around every gpd_step on the launch stream for the per-launch kernel time (skipped
+    without `kernel_time`).  `after_timed()` runs between the two passes.
+    Returns (wall seconds, mean kernel us or None)."""
     P = pool.shape[0]
     for k in range(warmup):
         sim.step(pool[k % P])
@@ -374,6 +395,10 @@ def time_steps(sim, pool, steps, warmup):
     wall = time.perf_counter() - t0
     if torch.distributed.is_initialized():
         torch.distributed.barrier()
+    if after_timed is not None:
+        after_timed()
+    if not kernel_time:
+        return wall, None
     stream = torch.cuda.current_stream(sim.device)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
     for k in range(steps):
@@ -757,6 +782,54 @@ def make_pool(E, A, device, seed, pool=64):
     return (torch.rand((pool, E, 1, A), generator=g, device=device) * 2 - 1).contiguous()
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6     # --dump-outputs: all files of all ranks together, headers included
+DUMP_HEADER_BYTES = 6 * 128          # one .npy header per file of a rank
+
+
+class OutputSnapshot:
+    """--dump-outputs: the sim-owned step outputs as a caller of the timed path holds them after
+    its last timed step, copied on the device right after the timed region (``take``) and written
+    later (``write``), outside everything that is timed.  An env batch whose float32 rows exceed
+    this rank's share of DUMP_BUDGET_BYTES is sampled: a fixed, seeded, sorted choice of envs, the
+    same in every run."""
+
+    def __init__(self, sim, world):
+        E, row = sim.n_envs, 2 * sim.drones_per_env * sim.obs_width * 4 + 3 * 4
+        budget = DUMP_BUDGET_BYTES // max(1, world) - DUMP_HEADER_BYTES
+        self.sim, self.index, self.fields = sim, None, None
+        if E * row > budget:
+            n = max(1, budget // (row + 8))
+            self.index = np.sort(np.random.default_rng(0).choice(E, n, replace=False))
+            self._index_dev = torch.from_numpy(self.index).to(sim.device)
+
+    def take(self):
+        s = self.sim
+        f = {"obs": s.obs, "reward": s.reward, "terminated": s.terminated, "truncated": s.truncated,
+             "terminal_obs": s.terminal_obs}
+        if self.index is not None:
+            f = {k: v.index_select(0, self._index_dev) for k, v in f.items()}
+        else:
+            f = {k: v.clone() for k, v in f.items()}
+        torch.cuda.synchronize(s.device)
+        self.fields = f
+
+    def write(self, out_dir, rank):
+        """Write <name>.npy (rank 0) or <name>_rank<r>.npy; returns {file name: shape}."""
+        os.makedirs(out_dir, exist_ok=True)
+        f = {k: v.cpu().numpy() for k, v in self.fields.items()}
+        done = (f["terminated"] | f["truncated"]).astype(bool)
+        f["terminal_obs"] = np.where(done[:, None, None], f["terminal_obs"], np.float32(0.0))
+        arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in f.items()}
+        if self.index is not None:
+            arrays["env_index"] = self.index.astype(np.float64)
+        written = {}
+        for name, a in arrays.items():
+            fname = f"{name}.npy" if rank == 0 else f"{name}_rank{rank}.npy"
+            np.save(os.path.join(out_dir, fname), a)
+            written[fname] = list(a.shape)
+        return written
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1,
@@ -767,6 +840,14 @@ def parse_args(argv=None):
     ap.add_argument("--act", default="rpm", choices=["rpm", "one_d_rpm"])
     ap.add_argument("--precision", default="f64", choices=["f32", "f64"],
                     help="f64 (default) is the parity-gated path (<=1e-10 vs the fp64 oracle)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (obs, reward, terminated, truncated, "
+                         "terminal_obs) as DIR/<name>.npy, float32, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's timing also run every other leg: kernel time and roofline, "
+                         "eager and the other launch form, strong scaling, hand-off, latency model, rollout, "
+                         "large-N sweep, other configs, CPU baselines and state parity (minutes; the --no-* "
+                         "options leave legs out of it)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-procs", type=int, default=0,
                     help="processes of the all-core CPU baseline (0 = the CPUs this job may use)")
@@ -909,32 +990,36 @@ def _run(args):
                            autoreset=True, device=device)
     nsub = sim.pyb_steps_per_ctrl
     pool = make_pool(E, A, device, seed=rank_seed(1000, rank))
-    # (1) eager pass (also the SB3-style per-call number); per-launch event pairs
-    eager_wall, eager_kern_us = time_steps(sim, pool, args.steps, args.warmup)
-    # (2) timed pass: the same steps replayed from a hipGraph (no host launch overhead); the
-    #     roofline's kernel duration comes from the events around these replays
-    # the other launch form beside it (same K; native loop when graphs are timed, and back), run
-    # first: native launches issued after graph replays measured slower
-    n_wall, n_steps, n_kern = (time_native if args.mode != "native" else time_graph)(sim, pool, args.steps, args.warmup)
-    if args.mode == "eager":
-        wall, steps_run, kern_us = eager_wall, args.steps, eager_kern_us
-    elif args.mode == "native":
-        wall, steps_run, kern_us = time_native(sim, pool, args.steps, args.warmup)
+    full = args.full
+    args.steps = max(1, args.steps)
+    snap = OutputSnapshot(sim, world) if args.dump_outputs else None
+    take = snap.take if snap is not None else None
+    headline = {"eager": time_steps, "native": time_native, "graph": time_graph}[args.mode]
+    if full:
+        # (1) eager pass (also the SB3-style per-call number); per-launch event pairs
+        eager_wall, eager_kern_us = time_steps(sim, pool, args.steps, args.warmup,
+                                               after_timed=take if args.mode == "eager" else None)
+        # (2) timed pass: the same steps replayed from a hipGraph (no host launch overhead); the
+        #     roofline's kernel duration comes from the events around these replays
+        # the other launch form beside it (same K; native loop when graphs are timed, and back), run
+        # first: native launches issued after graph replays measured slower
+        n_wall, n_steps, n_kern = (time_native if args.mode != "native" else time_graph)(sim, pool, args.steps,
+                                                                                         args.warmup)
+        if args.mode == "eager":
+            wall, steps_run, kern_us = eager_wall, args.steps, eager_kern_us
+        else:
+            wall, steps_run, kern_us = headline(sim, pool, args.steps, args.warmup, after_timed=take)
     else:
-        wall, steps_run, kern_us = time_graph(sim, pool, args.steps, args.warmup)
-    other_leg = {"mode": "native" if args.mode != "native" else "graph", "ms_per_step": 1000.0 * n_wall / n_steps,
-                 "value": E * nsub * n_steps / n_wall, "kernel_us_per_launch_events": n_kern}
+        # a plain run: the warm-up, the timed steps and nothing else
+        timed = headline(sim, pool, args.steps, args.warmup, kernel_time=False, after_timed=take)
+        wall, steps_run = timed[0], args.steps
     wall = max_over_ranks(wall, device)
-    eager_wall = max_over_ranks(eager_wall, device)
     drone_dt = world * E * nsub * steps_run
     value = drone_dt / wall
     ms_per_step = 1000.0 * wall / steps_run
-    rbytes = 8 if args.precision == "f64" else 4
-    alg = alg_bytes_per_drone_step(args.act, rbytes) * E
-    achieved = alg / (kern_us * 1e-6) / 1e9
     result = {
         "metric": "env-steps/sec (drone·dt) at 4096 envs, 1/2/4/8 GPU; state L2 vs PyBullet",
-        "value": value, "unit": "drone*dt/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "value": value, "unit": "drone*dt/s", "n_gpus": world, "steps": steps_run, "warmup": args.warmup,
         "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32" if args.precision == "f32" else "f64", "data": "synthetic",
         "mode": {"eager": "one Python BatchedAviarySim.step() call per env.step",
@@ -944,6 +1029,40 @@ def _run(args):
                                f"240/30 Hz = {nsub} substeps/step, U[-1,1] actions, SB3 auto-reset)",
                    "n_envs_per_gpu": E, "global_envs": E * world, "drones_per_env": 1,
                    "parallelism": f"env-sharded x{world} (no collective in the step loop)"},
+        "ctrl_steps_per_s": world * E * steps_run / wall,
+        "full": full,
+    }
+    if snap is not None:
+        files = snap.write(args.dump_outputs, rank)
+        result["outputs"] = {"dir": args.dump_outputs, "files": files,
+                             "sampled_envs": None if snap.index is None else int(snap.index.size)}
+    if not full:
+        sim.close()
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return result if rank == 0 else None
+    return _full_legs(args, result, sim, device, world, rank, kern_us, eager_wall, eager_kern_us,
+                      (n_wall, n_steps, n_kern))
+
+
+def _full_legs(args, result, sim, device, world, rank, kern_us, eager_wall, eager_kern_us, other):
+    """--full: every leg beside the headline line, added to `result` (rank 0 returns it)."""
+    from gym_pybullet_drones_routing_amd.enums import ActionType
+    from gym_pybullet_drones_routing_amd.shard import max_over_ranks, rank_seed
+    from gym_pybullet_drones_routing_amd.sim import BatchedAviarySim
+
+    E = args.envs
+    A = 4 if args.act == "rpm" else 1
+    nsub = sim.pyb_steps_per_ctrl
+    value = result["value"]
+    n_wall, n_steps, n_kern = other
+    other_leg = {"mode": "native" if args.mode != "native" else "graph", "ms_per_step": 1000.0 * n_wall / n_steps,
+                 "value": E * nsub * n_steps / n_wall, "kernel_us_per_launch_events": n_kern}
+    eager_wall = max_over_ranks(eager_wall, device)
+    rbytes = 8 if args.precision == "f64" else 4
+    alg = alg_bytes_per_drone_step(args.act, rbytes) * E
+    achieved = alg / (kern_us * 1e-6) / 1e9
+    result.update({
         "kernel_us": kern_us,
         "timed_region_note": ("a timed region carries a fixed ~18 us HIP round trip (graph launch -> first kernel, "
                               "completion -> synchronize return), ~0.9 us/step at K = 20; per-step cost without it "
@@ -951,13 +1070,12 @@ def _run(args):
         "eager": {"ms_per_step": 1000.0 * eager_wall / args.steps,
                   "value": world * E * nsub * args.steps / eager_wall,
                   "kernel_us_per_launch_events": eager_kern_us},
-        "ctrl_steps_per_s": world * E * args.steps / wall,
         "other_launch_form": other_leg,
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBPS, "traffic": None, "traffic_unit": "bytes per launch",
                      "kernel": step_kernel_name(sim, rbytes, args.act),
                      "alg_bytes_per_launch": alg},
-    }
+    })
 
     grid_lanes = -(-sim.n_drones // sim.constants.drones_per_block) * sim.constants.lanes_per_block  # launch geometry
     result["roofline"]["grid_lanes"] = grid_lanes

@@ -14,7 +14,7 @@ i=0
 for E in ${AB_ENVS:-4096}; do
   for val in ${AB_VALS:-"0 1 0 1"}; do
     i=$((i+1))
-    env ${AB_VAR:-GPD_NOTHING}=$val timeout -k 10 300 python bench.py --no-cpu-baseline --no-sweep --envs $E --steps ${AB_STEPS:-2000} --warmup 100 \
+    env ${AB_VAR:-GPD_NOTHING}=$val timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-sweep --envs $E --steps ${AB_STEPS:-2000} --warmup 100 \
       > $OUT/run${i}_${E}_${val}.json 2> $OUT/run${i}_${E}_${val}.err || exit $?
   done
 done

@@ -3,7 +3,7 @@
 # Jobs (each GPU step under its own timeout; the first failure ends the call):
 #   tests          pytest -m gpu in one process (TEST_PATHS / PYTEST_ARGS narrow it)
 #   smoke          __graft_entry__.smoke()
-#   bench          bench.py (the driver's default line) -> bench.json
+#   bench          bench.py --full (the headline line and every other leg) -> bench.json
 #   traces         rocprofv3 --kernel-trace --stats of the bench command and of the sweep
 #   pmc_bytes      FETCH_SIZE / WRITE_SIZE passes (separate runs) over the 4096 .. 4M env steps
 #   probe          scripts/contact_probe.py $PROBE_CASES with every library of $LIBS, alternated
@@ -13,7 +13,7 @@
 #                  headline step for each library of $LIBS
 #   pmc_probe      one PMC pass per counter group of $PMC_GROUPS (';'-separated) and library of $LIBS
 #                  over contact_probe.py $PROBE_CASES (PROBE_STEPS / PROBE_WARM shorten it)
-#   ab             bench.py --no-cpu-baseline --steps 300 with every library of $LIBS, alternated
+#   ab             bench.py --full --no-cpu-baseline --steps 300 with every library of $LIBS, alternated
 #   rollout        scripts/prof_rollout.py (bench.py's RL-rollout leg) for each store policy of
 #                  $POLICIES (gpd_config::store_policy, 0 = library default), alternated $REPS times
 #   rollout_trace  rocprofv3 --kernel-trace --stats of prof_rollout.py for each policy of $POLICIES
@@ -36,12 +36,12 @@ job_tests() {
   local rc=$?; echo "pytest rc=$rc" >> $OUT/gpu_tests.log; return $rc
 }
 job_smoke() { timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; }
-job_bench() { timeout -k 10 600 python bench.py ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err; }
+job_bench() { timeout -k 10 600 python bench.py --full ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err; }
 job_traces() {
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_bench -o bench --output-format csv -- \
-    python3 bench.py --no-cpu-baseline --no-sweep --no-latency-model --no-rollout > $OUT/prof_bench_stdout.json 2> $OUT/prof_bench.err || return $?
+    python3 bench.py --full --no-cpu-baseline --no-sweep --no-latency-model --no-rollout > $OUT/prof_bench_stdout.json 2> $OUT/prof_bench.err || return $?
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_sweep -o sweep --output-format csv -- \
-    python3 bench.py --no-cpu-baseline > $OUT/prof_sweep_stdout.json 2> $OUT/prof_sweep.err
+    python3 bench.py --full --no-cpu-baseline > $OUT/prof_sweep_stdout.json 2> $OUT/prof_sweep.err
 }
 job_pmc_bytes() {
   for E in 4096 65536 1048576 4194304; do
@@ -92,7 +92,7 @@ job_pmc_probe() {
 job_ab() {
   for rep in $(seq $REPS); do
     for v in $LIBS; do
-      GPD_ALLOW_ABI_MISMATCH=1 GPD_LIB=$(libpath $v) timeout -k 10 300 python bench.py --no-cpu-baseline --steps 300 \
+      GPD_ALLOW_ABI_MISMATCH=1 GPD_LIB=$(libpath $v) timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 300 \
         ${BENCH_ARGS} > $OUT/ab_${v}_r$rep.json 2> $OUT/ab_${v}_r$rep.err || return $?
     done
   done
