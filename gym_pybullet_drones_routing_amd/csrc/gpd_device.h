@@ -219,6 +219,30 @@ __device__ __forceinline__ DynK<R> dyn_consts(const Consts<R>& c, int warm0 = 0,
   return k;
 }
 
+// The constants of the duo kernel's pose-wave epilogue (task target, reset template with its
+// Euler angles, the xy bound), held in VGPRs from entry: their scalar loads go out as a second
+// batch right behind dyn_consts' wait (the two pins exceed one asm statement's 30 operands), still
+// under the state loads; the loads land ~100 cycles later for it.  Fetched where they are used -
+// behind the last hand-off, inside the task and reset branches - each is a scalar-cache miss (the
+// cache is cold at every launch) the wave waits out on the block's critical path.
+template <typename R>
+struct TailK {
+  R tg[3], ini[10], bound_xy;
+};
+template <typename R>
+__device__ __forceinline__ TailK<R> tail_consts(const Consts<R>& c, R bound_xy) {
+  TailK<R> t;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) t.tg[k] = c.target0[k];
+#pragma unroll
+  for (int k = 0; k < 10; ++k) t.ini[k] = c.init0[k];
+  t.bound_xy = bound_xy;
+  asm volatile("" : "+v"(t.tg[0]), "+v"(t.tg[1]), "+v"(t.tg[2]), "+v"(t.ini[0]), "+v"(t.ini[1]), "+v"(t.ini[2]),
+               "+v"(t.ini[3]), "+v"(t.ini[4]), "+v"(t.ini[5]), "+v"(t.ini[6]), "+v"(t.ini[7]), "+v"(t.ini[8]),
+               "+v"(t.ini[9]), "+v"(t.bound_xy));
+  return t;
+}
+
 template <typename R>
 struct Drone {
   R px, py, pz;            // base position (physics-client copy == self.pos)

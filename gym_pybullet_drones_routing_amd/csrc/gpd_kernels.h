@@ -91,6 +91,8 @@ __device__ unsigned long long g_stamps[65536 * kStampPhases];
 // memory when the wave stores them, so less of that write-back is left for the kernel's end.
 typedef int gpd_v4i __attribute__((ext_vector_type(4)));
 typedef unsigned gpd_v2u __attribute__((ext_vector_type(2)));
+typedef int gpd_v2i __attribute__((ext_vector_type(2)));
+typedef float gpd_v4f __attribute__((ext_vector_type(4)));
 #ifndef GPD_WT_AUX
 #define GPD_WT_AUX 16   // sc1 (write-through); diagnostic builds try other cache-policy bits
 #endif
@@ -116,6 +118,7 @@ __device__ __forceinline__ void store_wt(__amdgpu_buffer_rsrc_t r, int off, doub
 
 typedef __attribute__((address_space(3))) void* lds_void_ptr;
 typedef __attribute__((address_space(1))) void* gbl_void_ptr;
+#define gpd_global __attribute__((address_space(1)))
 
 // Downwash work split for blocks with idle lanes: with n > 0, the block's n = tpb*D drone
 // pairs are spread over all 64 lanes (pair k: drone k/D of the block, neighbour k%D of its
@@ -254,10 +257,67 @@ __device__ __forceinline__ void mark_last_in_ring(const SimView<R>& v, long long
   if ((v.wt & 4) && n == 0) v.ctr[v.N / v.D] = make_int2(1, 0);
 }
 
+// step_kernel_duo's forms of the two above: the drone's state address (st = v.state + tidx(n, 0,
+// kStateComps), o its byte offset for the write-through form) and the ctr slot come from the
+// caller, which forms them ahead of its final barrier.  Its envs are single drones, so the slot
+// N / D is N.  (Separate functions: the other kernels' code stays as it was.)
+template <typename R, int AUX = kAuxWt, typename P = R*>
+__device__ __forceinline__ void store_drone_step_at(const SimView<R>& v, P st, int o, const Drone<R>& s,
+                                                    const R last[4]) {
+  if (v.wt & 2) {
+    const __amdgpu_buffer_rsrc_t r =
+        __builtin_amdgcn_make_buffer_rsrc(v.state, 0, (int)(kStateComps * v.npad * (long long)sizeof(R)), 0x00020000);
+    const R vals[20] = {s.px, s.py, s.pz, s.qx, s.qy, s.qz, s.qw, s.vx, s.vy, s.vz,
+                        s.wx, s.wy, s.wz, s.ax, s.ay, s.az, last[0], last[1], last[2], last[3]};
+    const bool skip_last = (v.wt & 4) != 0;
+#pragma unroll
+    for (int k = 0; k < 20; ++k, o += 64 * (int)sizeof(R))
+      if (k < 16 || !skip_last) store_wt<AUX>(r, o, vals[k]);
+    return;
+  }
+  st[0 * 64] = s.px; st[1 * 64] = s.py; st[2 * 64] = s.pz;
+  st[3 * 64] = s.qx; st[4 * 64] = s.qy; st[5 * 64] = s.qz; st[6 * 64] = s.qw;
+  st[7 * 64] = s.vx; st[8 * 64] = s.vy; st[9 * 64] = s.vz;
+  st[10 * 64] = s.wx; st[11 * 64] = s.wy; st[12 * 64] = s.wz;
+  st[13 * 64] = s.ax; st[14 * 64] = s.ay; st[15 * 64] = s.az;
+  if (!(v.wt & 4)) {
+    st[16 * 64] = last[0]; st[17 * 64] = last[1]; st[18 * 64] = last[2]; st[19 * 64] = last[3];
+  }
+}
+template <typename R>
+__device__ __forceinline__ void mark_last_in_ring_single(const SimView<R>& v, long long n) {
+  if ((v.wt & 4) && n == 0) v.ctr[v.N] = make_int2(1, 0);
+}
+
+// |target - pos|^2 of step_kernel_duo's task hook: tx*tx + ty*ty + tz*tz in the very operations
+// the compiler has contracted it to in that kernel (f64: two chained fmas on ty*ty; f32: one
+// fma and a rounded tz*tz), written out so that a change of the code around it cannot change
+// how the sum is contracted, and with it the reward's last bit.  (The one-wave step_kernel keeps
+// the plain expression; should a compiler contract that one differently, the kernel-form tests of
+// tests/test_gpu_parity.py and tests/test_gpu_step_tail.py compare the rewards to a tolerance, and
+// `bench.py --dump-outputs` of two builds shows the last bit.)
+__device__ __forceinline__ double hover_d2(double tx, double ty, double tz) {
+#pragma clang fp contract(off)
+  return __builtin_fma(tz, tz, __builtin_fma(tx, tx, ty * ty));
+}
+__device__ __forceinline__ float hover_d2(float tx, float ty, float tz) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(ty, ty, tx * tx) + tz * tz;
+}
+
 // Workgroup barrier for LDS exchanges within a block (between its waves, or its lanes): waits for this wave's own
 // LDS operations only.  __syncthreads() (a workgroup release fence) would also wait for every
 // vector-memory operation in flight, including an LDS-DMA that nobody reads until much later.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// A wave-uniform pointer the compiler formed with vector instructions (a 64-bit multiply), back
+// in scalar registers.
+template <typename T>
+__device__ __forceinline__ T* uniform_ptr(T* p) {
+  const unsigned long long x = (unsigned long long)p;
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)x), hi = __builtin_amdgcn_readfirstlane((unsigned)(x >> 32));
+  return (T*)(((unsigned long long)hi << 32) | lo);
+}
 
 // LDS exchange among the lanes of ONE wave (the step / integrate kernels' blocks are one wave):
 // a wave's LDS instructions execute in order, so a later ds_read sees an earlier ds_write of
@@ -2289,45 +2349,132 @@ __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R*
       if (A == 4) *reinterpret_cast<float4*>(ring_cur) = make_float4(a[0], a[1], a[2], a[3]);
       else ring_cur[0] = a[0];
     }
+    // Everything the tail needs that does not depend on the DMA'd data is formed in the slack
+    // the wave has at the hand-off barriers (its tail is the end of the block's critical path)
+    // and pinned in registers across them:
+    //   * the DMA source of a lane as a 32-bit byte offset on a wave-uniform base (the block's
+    //     first 64-drone tile), stepped slot by slot with an add and a wrap;
+    //   * for the common case of a block whose nact * L elements fit one pass of U per lane
+    //     (`fits`): each element's LDS address, row and store offset;
+    //   * the rows' buffer base and size.
+    // Behind the last hand-off only m0 + global_load_lds per slot remain, behind vmcnt(0) only
+    // the LDS reads and the stores.  Where it runs: the wave is the block's last to start and must
+    // not be late at hand-off 0 (all of it in front of that barrier measured slower than no change,
+    // profiles/r7/step_tail/), so one half runs behind hand-off 0 and the other behind hand-off 1,
+    // each well inside a substep of the pose / rate waves.
+    constexpr int U = 4;                          // elements per lane in flight per pass
+    constexpr int EB = A == 4 ? 16 : 4;           // bytes of a tile element
+    constexpr unsigned kSlotBytes = 64u * A * 4u; // one ring slot of a 64-drone tile
+    const int total = nact * L;
+    const int NC = A == 4 ? 3 + L : v.W;          // row stride in elements
+    const int c0 = A == 4 ? 3 : 12;               // first history column
+    const float rL = 1.0f / (float)L;             // (g + 0.5) / L: exact row index for g < 2^12
+    const bool fits = total <= U * kWave;
+    const bool wt_rows = (v.wt & 1) != 0;
+    float* dst0;
+    int nrec;
+    const char* ring0;
+    unsigned dma_lo, dma_hi, dma_cur;
+    int off[U], row[U];
+    lds_void_ptr la[U];
+    // (lane, drone: opaque copies taken where a part runs, or the scheduler hoists the part's
+    // arithmetic above the barrier in front of it)
+    auto map_elem = [&](int u, int lane) {
+      // an element past the end gets an offset past num_records, so the buffer unit drops its store
+      const int g = lane + u * kWave;
+      const bool ok = g < total;
+      const int gg = ok ? g : total - 1;
+      const int i = (int)(((float)gg + 0.5f) * rL), k = gg - i * L;
+      row[u] = i;
+      off[u] = ok ? (i * NC + c0 + k) * EB : nrec;
+      la[u] = A == 4 ? (lds_void_ptr)(tile4 + (__umul24(k, kPad) + i)) : (lds_void_ptr)(tilef + (__umul24(k, kPad) + i));
+    };
+    auto pre_a = [&]() {
+      int lane = tid;
+      long long drone = nn;
+      asm volatile("" : "+v"(lane), "+v"(drone));
+      dst0 = uniform_ptr(io.obs + n0 * v.W);
+      nrec = __builtin_amdgcn_readfirstlane(nact * v.W * 4);
+      ring0 = uniform_ptr(reinterpret_cast<const char*>(v.ring + (n0 >> 6) * L * (64LL * A)));
+      dma_lo = (unsigned)((((drone >> 6) - (n0 >> 6)) * L * 64 + (drone & 63)) * (A * 4));
+      dma_hi = dma_lo + (unsigned)L * kSlotBytes;
+      dma_cur = dma_lo + (unsigned)(hd + 1 == L ? 0 : hd + 1) * kSlotBytes;
+      map_elem(0, lane);
+      map_elem(1, lane);
+      asm volatile("" : "+v"(dma_lo), "+v"(dma_hi), "+v"(dma_cur), "+v"(off[0]), "+v"(off[1]), "+v"(row[0]), "+v"(row[1]),
+                   "+v"(la[0]), "+v"(la[1]), "+s"(ring0), "+s"(dst0), "+s"(nrec));
+      // (the pinned scalars read back as wave-uniform, or the stores would loop over "distinct" bases)
+      dst0 = uniform_ptr(dst0);
+      nrec = __builtin_amdgcn_readfirstlane(nrec);
+    };
+    auto pre_b = [&]() {
+      int lane = tid;
+      asm volatile("" : "+v"(lane));
+      map_elem(2, lane);
+      map_elem(3, lane);
+      asm volatile("" : "+v"(off[2]), "+v"(off[3]), "+v"(row[2]), "+v"(row[3]), "+v"(la[2]), "+v"(la[3]));
+    };
     // This wave publishes nothing to the others, so its barriers skip lds_barrier's
     // lgkmcnt(0) wait: an LDS-DMA in flight holds that counter until it lands.
-    GPD_IOSTAMP(0);
     // (an LDS-counter hand-off between the pose and rate waves, which would free this wave of
     // their barriers, measured 5.3 / 6.4 us against 4.9: profiles/r6/duo_flags/)
+    GPD_IOSTAMP(0);
     asm volatile("s_barrier" ::: "memory");       // hand-off 0
     GPD_IOSTAMP(1);
-    for (int k = 1; k < nsub; ++k) asm volatile("s_barrier" ::: "memory");   // hand-offs 1 .. nsub-1
+    pre_a();
+    if (nsub > 1) asm volatile("s_barrier" ::: "memory");   // hand-off 1
+    pre_b();
+    for (int k = 2; k < nsub; ++k) asm volatile("s_barrier" ::: "memory");   // hand-offs 2 .. nsub-1
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(dst0, 0, nrec, 0x00020000);
+    auto tile_read4 = [&](int u) {
+      return __builtin_bit_cast(float4, *(const __attribute__((address_space(3))) gpd_v4f*)la[u]);
+    };
+    auto tile_read1 = [&](int u) { return *(const __attribute__((address_space(3))) float*)la[u]; };
     // history ring -> tile (LDS-DMA) behind the last hand-off: an LDS-DMA in flight while the
     // pose / rate waves still exchange hand-offs slowed their substeps by ~850 cycles per launch
     // (phase stamps, 4096 envs), issued here it lands beside the pose wave's last substep and
     // epilogue.  Slot head+1+m of every drone of the block -> tile column m (one coalesced
     // 64-drone run per slot, lane-contiguous in LDS).
-    {
-      const float* rb = v.ring + ridx(nn, 0, L, A);
-      int slot = hd + 1 == L ? 0 : hd + 1;
-      for (int m = 0; m < L - 1; ++m) {
-        const float* src = rb + slot * (64 * A);
-        if (A == 4) __builtin_amdgcn_global_load_lds((gbl_void_ptr)src, (lds_void_ptr)(tile4 + m * kPad), 16, 0, 0);
-        else __builtin_amdgcn_global_load_lds((gbl_void_ptr)src, (lds_void_ptr)(tilef + m * kPad), 4, 0, 0);
-        slot = slot + 1 == L ? 0 : slot + 1;
-      }
+    for (int m = 0; m < L - 1; ++m) {
+      const char* src = ring0 + dma_cur;
+      if (A == 4) __builtin_amdgcn_global_load_lds((gbl_void_ptr)src, (lds_void_ptr)(tile4 + m * kPad), 16, 0, 0);
+      else __builtin_amdgcn_global_load_lds((gbl_void_ptr)src, (lds_void_ptr)(tilef + m * kPad), 4, 0, 0);
+      dma_cur += kSlotBytes;
+      dma_cur = dma_cur == dma_hi ? dma_lo : dma_cur;
     }
     GPD_IOSTAMP(2);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA has landed in its tile
     GPD_IOSTAMP(3);
-    const int total = nact * L;
-    const int NC = A == 4 ? 3 + L : v.W;          // row stride in elements
-    const int c0 = A == 4 ? 3 : 12;               // first history column
-    const float rL = 1.0f / (float)L;             // (g + 0.5) / L: exact row index for g < 2^12
-    float* const dst0 = io.obs + n0 * v.W;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(dst0, 0, nact * v.W * 4, 0x00020000);
-    // four elements per lane in flight per pass (LDS reads, then stores); an element past the
-    // end gets an offset past num_records, so the buffer unit drops its store
-    constexpr int U = 4;
-    for (int g0 = tid; g0 < total; g0 += U * kWave) {
-      int off[U];
-      float4 v4[U];
-      float v1[U];
+    // (the fits pass keeps its elements in registers for the terminal rows: an LDS read behind
+    // the stores would make the compiler wait for every store in flight first)
+    float4 v4[U];
+    float v1[U];
+    if (fits) {
+      // one pass: LDS reads, then stores, both at the addresses formed at the hand-offs
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (A == 4) v4[u] = tile_read4(u);
+        else v1[u] = tile_read1(u);
+      }
+      if (wt_rows) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (A == 4) store_wt(rsrc, off[u], v4[u]);
+          else store_wt(rsrc, off[u], v1[u]);
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (A == 4) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(gpd_v4i, v4[u]), rsrc, off[u], 0, 0);
+          else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v1[u]), rsrc, off[u], 0, 0);
+        }
+      }
+    }
+    // longer histories: U elements per lane in flight per pass, the mapping formed per pass
+    for (int g0 = fits ? total : tid; g0 < total; g0 += U * kWave) {
+      int poff[U];
+      float4 p4[U];
+      float p1[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int g = g0 + u * kWave;
@@ -2335,18 +2482,18 @@ __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R*
         const int gg = ok ? g : total - 1;
         const int i = (int)(((float)gg + 0.5f) * rL), k = gg - i * L;
         const int e = i * NC + c0 + k;
-        off[u] = ok ? e * (A == 4 ? 16 : 4) : nact * v.W * 4;
-        if (A == 4) v4[u] = tile4[__umul24(k, kPad) + i];
-        else v1[u] = tilef[__umul24(k, kPad) + i];
+        poff[u] = ok ? e * (A == 4 ? 16 : 4) : nact * v.W * 4;
+        if (A == 4) p4[u] = tile4[__umul24(k, kPad) + i];
+        else p1[u] = tilef[__umul24(k, kPad) + i];
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         if (v.wt & 1) {
-          if (A == 4) store_wt(rsrc, off[u], v4[u]);
-          else store_wt(rsrc, off[u], v1[u]);
+          if (A == 4) store_wt(rsrc, poff[u], p4[u]);
+          else store_wt(rsrc, poff[u], p1[u]);
         } else {
-          if (A == 4) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(gpd_v4i, v4[u]), rsrc, off[u], 0, 0);
-          else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v1[u]), rsrc, off[u], 0, 0);
+          if (A == 4) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(gpd_v4i, p4[u]), rsrc, poff[u], 0, 0);
+          else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p1[u]), rsrc, poff[u], 0, 0);
         }
       }
     }
@@ -2356,7 +2503,17 @@ __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R*
     const unsigned long long dr = sdone;
     if (dr) {
       float* const tdst = io.terminal_obs + n0 * v.W;
-      for (int g = tid; g < total; g += kWave) {
+      if (fits) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (tid + u * kWave < total && ((dr >> row[u]) & 1ull)) {
+            char* const t = reinterpret_cast<char*>(tdst) + off[u];
+            if (A == 4) *reinterpret_cast<float4*>(t) = v4[u];
+            else *reinterpret_cast<float*>(t) = v1[u];
+          }
+        }
+      }
+      for (int g = fits ? total : tid; g < total; g += kWave) {
         const int i = (int)(((float)g + 0.5f) * rL), k = g - i * L;
         if ((dr >> i) & 1ull) {
           const int e = i * NC + c0 + k;
@@ -2466,8 +2623,20 @@ __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R*
   const int sc = cv.x;          // step_counter
   const int head = cv.y;        // ring slot receiving this step's action
   DynK<R> dk = dyn_consts(c, v.task, io.trunc);
+  const TailK<R> tk = tail_consts(c, v.bound_xy);
   const int nsub = dk.nsub;
   const int NC = A == 4 ? 3 + v.ring_len : 12 + v.ring_len * A;
+  // where the lane's results go: formed here, under the loads, not behind the final barrier
+  // (global-address-space pointers: a generic pointer out of the pin would make flat stores)
+  gpd_global R* st_out = (gpd_global R*)(v.state + tidx(nn, 0, kStateComps));
+  int st_off = (int)(tidx(nn, 0, kStateComps) * sizeof(R));
+  gpd_global float* rew_out = (gpd_global float*)(io.reward + nn);
+  gpd_global uint8_t* term_out = (gpd_global uint8_t*)(io.term + nn);
+  gpd_global uint8_t* trunc_out = (gpd_global uint8_t*)(io.trunc + nn);
+  gpd_global gpd_v2i* ctr_out = (gpd_global gpd_v2i*)(v.ctr + nn);
+  int head_next = head + 1 == v.ring_len ? 0 : head + 1;
+  asm volatile("" : "+v"(st_out), "+v"(st_off), "+v"(rew_out), "+v"(term_out), "+v"(trunc_out), "+v"(ctr_out),
+               "+v"(head_next));
 #ifdef GPD_STAMPS
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // diagnostic: loads landed
   GPD_STAMP(10);
@@ -2520,14 +2689,20 @@ __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R*
   float reward = -1.0f;
   bool term = false, trunc = false;
   if (v.task != TASK_NONE) {
-    const R* tg = c.target0;
-    const R tx = tg[0] - s.px, ty = tg[1] - s.py, tz = tg[2] - s.pz;
-    const R d2 = tx * tx + ty * ty + tz * tz;
+    const R tx = tk.tg[0] - s.px, ty = tk.tg[1] - s.py, tz = tk.tg[2] - s.pz;
+    const R d2 = hover_d2(tx, ty, tz);
     R r = R(2) - d2 * d2;
     r = r > R(0) ? r : R(0);
-    const bool oob = g_abs(s.px) > v.bound_xy || g_abs(s.py) > v.bound_xy || s.pz > R(2) || tilted;
+    const bool oob = g_abs(s.px) > tk.bound_xy || g_abs(s.py) > tk.bound_xy || s.pz > R(2) || tilted;
     reward = (float)r;
-    term = g_sqrt(d2) < R(1e-4);   // np.linalg.norm(...) < .0001 (HoverAviary.py:92)
+    // np.linalg.norm(...) < .0001 (HoverAviary.py:92).  A squared distance more than 1 % away
+    // from 1e-8 decides it (its root is then 0.5 % away from 1e-4, far beyond any rounding of
+    // the root); only a wave with a lane inside that band takes the square root, so the result
+    // is the root's comparison in every case and the 16-instruction dependent f64 root leaves
+    // the epilogue.
+    term = d2 < R(0.99e-8);
+    const bool band = !(d2 < R(0.99e-8)) && !(d2 > R(1.01e-8));   // a NaN goes the root's way, too
+    if (GPD_RARE(__ballot(band) != 0ull)) term = g_sqrt(d2) < R(1e-4);
     trunc = oob || sc >= v.trunc_sc;
   }
   const bool done = term || trunc;
@@ -2549,7 +2724,7 @@ __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R*
         for (int k = 0; k < 12; ++k) trow[k] = row12[k];
       }
     }
-    const R* ini = c.init0;
+    const R* ini = tk.ini;
     s.px = ini[0]; s.py = ini[1]; s.pz = ini[2];
     s.qx = ini[3]; s.qy = ini[4]; s.qz = ini[5]; s.qw = ini[6];
     s.vx = s.vy = s.vz = R(0);
@@ -2563,6 +2738,9 @@ __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R*
     for (int k = 6; k < 12; ++k) row12[k] = 0.0f;
   }
   const unsigned long long done_rows = __ballot(do_reset && active && io.terminal_obs != nullptr);
+  // what the last stores write, formed before the final barrier (the stores stay behind it)
+  int ctr_x = do_reset ? 0 : sc + nsub, term_b = term ? 1 : 0, trunc_b = trunc ? 1 : 0;
+  asm volatile("" : "+v"(ctr_x), "+v"(term_b), "+v"(trunc_b));
   if (IO) {
     // the row's 12 state columns straight from registers; the io wave writes the rest
     GPD_STAMP(5);
@@ -2610,12 +2788,12 @@ __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R*
   GPD_STAMP(7);
   GPD_RSTAMP(12);
   if (!active) return;
-  store_drone_step(v, n, s, last);
-  mark_last_in_ring(v, n);
-  io.reward[n] = reward;
-  io.term[n] = term ? 1 : 0;
-  io.trunc[n] = trunc ? 1 : 0;
-  v.ctr[n] = make_int2(do_reset ? 0 : sc + nsub, head + 1 == v.ring_len ? 0 : head + 1);
+  store_drone_step_at<R, kAuxWt>(v, st_out, st_off, s, last);
+  mark_last_in_ring_single(v, n);
+  *rew_out = reward;
+  *term_out = (uint8_t)term_b;
+  *trunc_out = (uint8_t)trunc_b;
+  *ctr_out = gpd_v2i{ctr_x, head_next};
 }
 
 // ---------------------------------------------------------------------------------------
