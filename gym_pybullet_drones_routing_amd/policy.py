@@ -78,13 +78,20 @@ def _linears(seq):
     return lin
 
 
+def _as_int64(x):
+    """``x`` mod 2^64 as the int64 with the same bits (the device words are uint64, torch's int64)."""
+    x = int(x) & 0xFFFFFFFFFFFFFFFF
+    return x - (1 << 64) if x >= 1 << 63 else x
+
+
 class MlpPolicyKernel:
     """The actor-critic ``module`` (``.pi``, ``.vf`` as Linear-Tanh-Linear-Tanh-Linear, ``.log_std``;
     examples/learn.py's ``ActorCritic``) as one rollout kernel per step.  The parameters are read
     in place: an optimizer step that updates them in place is seen by the next call (and by a
-    captured graph).  ``seed``: the Philox key; the call counters (one per group of 16 rows) live
-    on the device (``rng``), sized for ``max_rows`` rows (grown by a call with more rows, which a
-    captured graph must not do)."""
+    captured graph).  ``seed``: the 64-bit Philox key, taken mod 2^64 (``rng[0]`` holds it as int64
+    two's complement: the kernel reads both 32-bit halves); the call counters (one per group of 16
+    rows) live on the device (``rng``), sized for ``max_rows`` rows (grown by a call with more rows,
+    which a captured graph must not do)."""
 
     def __init__(self, module, seed=0, max_rows=1 << 16):
         self._lib = load()
@@ -112,7 +119,7 @@ class MlpPolicyKernel:
         self._st = st
         # {key, 0, call counter of row group 0, 1, ...} (include/gpd_policy.h)
         self.rng = torch.zeros(2 + -(-int(max_rows) // GROUP_ROWS), dtype=torch.int64, device=dev)
-        self.rng[0] = int(seed)
+        self.rng[0] = _as_int64(seed)
 
     @property
     def rng_groups(self):

@@ -21,7 +21,33 @@ NCCL_FLOAT32 = 7
 
 
 class UniqueId(ctypes.Structure):
-    _fields_ = [("internal", ctypes.c_char * NCCL_UNIQUE_ID_BYTES)]
+    # raw bytes, not c_char: ctypes reads a c_char array as a C string and stops at the first NUL
+    _fields_ = [("internal", ctypes.c_ubyte * NCCL_UNIQUE_ID_BYTES)]
+
+
+def uid_to_bytes(uid):
+    """All 128 bytes of an ncclUniqueId, NULs included."""
+    return ctypes.string_at(ctypes.addressof(uid), NCCL_UNIQUE_ID_BYTES)
+
+
+def uid_from_bytes(raw):
+    """The ncclUniqueId holding exactly these 128 bytes."""
+    if not isinstance(raw, (bytes, bytearray)) or len(raw) != NCCL_UNIQUE_ID_BYTES:
+        got = f"{len(raw)} bytes" if isinstance(raw, (bytes, bytearray)) else type(raw).__name__
+        raise ValueError(f"an ncclUniqueId is exactly {NCCL_UNIQUE_ID_BYTES} bytes, got {got}")
+    uid = UniqueId()
+    ctypes.memmove(ctypes.addressof(uid), bytes(raw), NCCL_UNIQUE_ID_BYTES)
+    return uid
+
+
+def exchange_uid(uid, rank, world):
+    """The rendezvous: rank 0's id reaches every rank of the torch.distributed group (one object
+    broadcast; nothing to do for a world of one).  ``uid`` is read on rank 0 only."""
+    if world <= 1:
+        return uid
+    box = [uid_to_bytes(uid) if rank == 0 else None]
+    dist.broadcast_object_list(box, src=0)
+    return uid_from_bytes(box[0])
 
 
 _lib = None
@@ -80,10 +106,7 @@ class RcclComm:
         uid = UniqueId()
         if self.rank == 0:
             _check(self.lib, "ncclGetUniqueId", self.lib.ncclGetUniqueId(ctypes.byref(uid)))
-        if self.world > 1:
-            box = [bytes(uid.internal) if self.rank == 0 else None]
-            dist.broadcast_object_list(box, src=0)
-            uid.internal = box[0]
+        uid = exchange_uid(uid, self.rank, self.world)
         self.comm = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             _check(self.lib, "ncclCommInitRank",

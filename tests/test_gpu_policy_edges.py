@@ -1,0 +1,590 @@
+"""The fused rollout policy kernel (csrc/gpd_policy.hip) against tests/policy_ref.py, a float64 host
+restatement of gpd_policy_rollout_step, at the shapes and modes where the kernel takes another path.
+
+What pins the kernel here:
+  * a float64 forward (forward64), with the float32 forward of the same network as the yardstick
+    of the tolerance: e_ref = forward32 - forward64 on the same batch, and the gates
+    max|kernel - forward64| <= 4 max|e_ref| and rms(kernel - forward64) <= 4 rms(e_ref) per output
+    kind (actions, values, bootstrapped rewards).  The actor's output layer has gain 1 (not
+    learn.py's 0.01), so |mu| crosses 1 and the deterministic clip acts; a quarter of the rows are
+    scaled until a layer-1 pre-activation reaches |z| = 6 (saturated tanh);
+  * the exact Philox4x32-10 / Box-Muller stream (std_normal64): which counter word (row, a >> 2,
+    call low / high) and key word (seed low / high) every lane uses, per row group's own counter:
+    |act - (mu_k + eps * exp(log_std))| <= 4 b + 2 u |act|, u = 2^-24,
+    b = exp(log_std) (8e-7 rad + 3e-7 |eps|) (the float32 angle 6.2831855f * u1: two roundings,
+    5.6e-7 absolute; logf, sqrtf, sincosf at 2 ulp each); a wrong word is an O(1) error;
+  * geometry independence: rows of a 65 541-row call (every block takes two trips round the
+    grid-stride loop, block 0 a third, ragged one) are bit-identical to the same rows in small calls;
+  * guards: every output is a view [16 : 16 + E] of a tensor with 16 sentinel rows before and after
+    it, every input likewise with NaN guards; guards of requested outputs, outputs not requested
+    and inputs are bit-unchanged after each call.  Terminal rows that are not bootstrapped hold NaN
+    (gpd_step leaves them untouched: in real use they are stale) and no output may hold one.
+
+Which test reaches what:
+  test_shape_sweep             all six KQ buckets (8, 16, 18, 24, 36, 48), n_obs 1 .. 192, n_act 1 .. 8,
+                               forward<T,T,T> and <T,T,F>; float4, float2 and scalar load_slice
+  test_misaligned_parameters   the float2 and scalar fallbacks of load_slice for W1 and W2
+  test_modes                   forward<T,T,T>, <T,T,F>, <F,T,T>, <F,T,F>, <F,F,T>; partial outputs
+  test_grid_stride             second and third trip of the grid-stride loop, both modes
+  test_exact_random_stream     the sampler, row > 2^16, a >> 2 = 1, counters with a high word
+  test_seed_is_taken_mod_2_64  a key of all ones
+
+Measured on an MI355X: max|e_ref| and, after it, the kernel's error as a multiple of e_ref (max / rms),
+for mu, for the value and for the bootstrapped rewards.  No gate had to be widened: the largest
+ratio anywhere is 2.65 (max) / 2.26 (rms), both on bootstrapped rewards, where a handful of rows
+are compared; mu and the value stay below 1.8.
+  shape sweep, E = 37 (n_obs x n_act)
+      1x1    mu 1.5e-7 1.10/1.08   v 1.8e-7 0.37/0.38   rew 6.4e-8 1.15/1.13
+      9x2    mu 1.9e-7 0.90/0.98   v 1.6e-7 0.90/1.10   rew 1.8e-7 1.67/1.44
+      32x3   mu 3.0e-7 0.83/0.86   v 2.3e-7 1.03/1.19   rew 1.4e-7 1.33/1.27
+      54x4   mu 3.2e-7 1.13/1.05   v 2.3e-7 1.09/0.94   rew 1.6e-7 0.85/0.85
+      64x5   mu 4.2e-7 0.81/0.92   v 3.5e-7 0.98/0.73   rew 1.7e-7 1.69/2.19
+      70x6   mu 3.5e-7 1.07/1.01   v 2.5e-7 0.98/0.88   rew 2.3e-7 0.51/0.62
+      72x7   mu 3.5e-7 1.17/0.98   v 3.2e-7 1.01/0.89   rew 1.5e-7 1.81/1.60
+      73x8   mu 3.3e-7 1.15/1.03   v 2.6e-7 1.19/1.28   rew 1.5e-7 1.00/1.19
+      81x1   mu 3.1e-7 0.95/1.05   v 3.3e-7 0.77/1.03   rew 1.2e-7 0.74/0.72
+      96x2   mu 5.0e-7 0.75/0.82   v 2.8e-7 0.93/1.10   rew 1.5e-7 1.96/1.72
+      108x3  mu 7.3e-7 0.51/0.76   v 3.4e-7 0.99/0.97   rew 9.8e-8 2.65/1.84
+      141x4  mu 3.9e-7 1.40/1.11   v 2.8e-7 1.45/1.16   rew 1.2e-7 2.52/2.15
+      145x5  mu 4.9e-7 1.34/1.00   v 2.9e-7 1.26/1.20   rew 1.8e-7 1.85/1.60
+      191x6  mu 5.9e-7 0.75/0.82   v 4.3e-7 1.44/1.08   rew 2.0e-7 1.97/1.49
+      192x7  mu 4.5e-7 1.58/1.14   v 3.0e-7 1.61/1.18   rew 1.3e-7 1.07/1.18
+      27x8   mu 3.2e-7 1.39/1.00   v 2.9e-7 0.75/0.84   rew 1.7e-7 1.00/1.18
+  misaligned parameters, E = 37
+      72x4   mu 3.3e-7 0.98/1.00   v 2.8e-7 1.24/1.54
+      96x2   mu 3.5e-7 1.02/0.84   v 2.1e-7 1.74/1.56
+  modes, E = 53 (the critic-only and bootstrap-only calls give the full call's figures exactly)
+      27x3   mu 2.9e-7 1.45/1.06   v 2.0e-7 1.14/1.00   rew 1.2e-7 1.72/1.29
+      144x6  mu 5.6e-7 0.85/0.96   v 3.9e-7 1.08/1.13   rew 1.5e-7 1.89/2.26
+  grid stride, E = 65 541
+      27x1   mu 5.7e-7 0.75/0.98   v 4.7e-7 1.12/0.97   rew 4.0e-7 0.97/1.00
+      144x8  mu 1.1e-6 0.90/0.86   v 8.2e-7 1.04/0.99   rew 4.8e-7 1.05/1.01
+  sampled actions, largest error as a fraction of the tolerance 4 b + 2 u |act|:
+      27x1x333 0.10   54x5x333 0.14   144x8x333 0.19   144x8x65541 0.32   (seed 2^64 - 1: 0.11)
+Wrong-on-purpose builds of the library, tried once: a dropped high call word fails
+test_exact_random_stream only; a bootstrap-only loop that re-reads its first group instead of the
+next fails test_grid_stride only; critic-only calls that skip the bootstrap chain fail test_modes
+(and the sharded self-comparison of tests/test_gpu_dist.py).  tests/test_gpu_policy.py passed all three.
+"""
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from tests import policy_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
+
+G = 16                      # guard rows on either side
+SENT = -777.25              # what outputs and their guards hold before a call
+NAN = float("nan")
+U = 2.0 ** -24
+OUT_NAMES = ("act_env", "buf_obs", "buf_act", "buf_logp", "buf_val", "buf_rew", "buf_done")
+SEED = (0x01234567 << 32) | 0x89ABCDEF
+
+
+def _module(n_obs, n_act, seed):
+    """learn.py's ActorCritic with an actor output gain of 1 and tests/test_gpu_policy.py's non-zero
+    biases and log-std, built on the CPU (the same everywhere), then moved to the GPU."""
+    import learn
+    torch.manual_seed(seed)
+    pol = learn.ActorCritic(n_obs, n_act)
+    with torch.no_grad():
+        torch.nn.init.orthogonal_(pol.pi[4].weight, gain=1.0)
+        for p in pol.parameters():
+            if p.dim() == 1:
+                p.copy_(0.1 * torch.randn_like(p))
+    return pol.cuda()
+
+
+def _rows(pol, E, n_obs, seed, extremes):
+    """[E, n_obs] float32 rows on the CPU: 0.7 N(0, 1), every fourth row scaled so that its largest
+    layer-1 pre-activation is 6; with ``extremes`` rows 1 and 2 are the rows of a larger pool with
+    the largest and the smallest mu (so a small batch is clipped on both sides)."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn((E + (256 if extremes else 0), n_obs), generator=g) * 0.7
+    w1 = pol.pi[0].weight.detach().cpu().double()
+    z = x.double() @ w1.T
+    x[::4] *= (6.0 / z.abs().amax(dim=1).clamp_min(1e-6))[::4, None].float()
+    if extremes:
+        mu, _ = ref.forward64(pol, x)
+        pick = x[[int(mu.max(1).argmax()), int(mu.min(1).argmin())]].clone()
+        x[1], x[2] = pick[0], pick[1]
+    return x[:E].contiguous()
+
+
+def _prev(pol, E, n_obs, seed, p_trunc):
+    """The previous step on the CPU: reward, terminated, truncated, terminal rows.  Row 0 and the
+    last row are bootstrapped, row 5 is truncated AND terminated (not bootstrapped), rows 16 .. 31
+    (one whole group) hold no truncation; every terminal row that is not bootstrapped is NaN."""
+    g = torch.Generator().manual_seed(seed)
+    rew = torch.rand(E, generator=g) * 2
+    te = (torch.rand(E, generator=g) < 0.1).to(torch.uint8)
+    tr = (torch.rand(E, generator=g) < p_trunc).to(torch.uint8)
+    tr[0], te[0], tr[E - 1], te[E - 1] = 1, 0, 1, 0
+    tr[5], te[5] = 1, 1
+    tr[16:32] = 0
+    tobs = _rows(pol, E, n_obs, seed + 1, False)
+    tobs[~(tr.bool() & ~te.bool())] = NAN
+    return rew, te, tr, tobs
+
+
+def _bits(t):
+    return t.view(torch.int32) if t.dtype == torch.float32 else t
+
+
+class Guarded:
+    """A contiguous [E, ...] device view ``t`` with 16 guard rows before and after it."""
+
+    def __init__(self, E, tail=(), data=None, guard=SENT, dtype=torch.float32):
+        self.E = E
+        self.full = torch.full((E + 2 * G,) + tuple(tail), guard, dtype=dtype, device="cuda")
+        self.t = self.full[G:G + E]
+        assert self.t.is_contiguous()
+        self.data = data              # the CPU rows the view holds (None: the sentinel)
+        if data is not None:
+            assert data.dtype == dtype and tuple(data.shape) == tuple(self.t.shape)
+            self.t.copy_(data)
+        else:
+            self.t.fill_(SENT)
+        self.guards = (self.full[:G].clone(), self.full[G + E:].clone())
+
+    def guards_intact(self):
+        return torch.equal(_bits(self.full[:G]), _bits(self.guards[0])) and \
+            torch.equal(_bits(self.full[G + self.E:]), _bits(self.guards[1]))
+
+    def untouched(self):
+        if self.data is None:
+            same = bool((self.t == SENT).all())
+        else:
+            same = torch.equal(_bits(self.t.cpu()), _bits(self.data))
+        return same and self.guards_intact()
+
+    def np(self):
+        return self.t.cpu().numpy()
+
+
+def _outputs(E, n_obs, n_act):
+    tails = {"act_env": (n_act,), "buf_obs": (n_obs,), "buf_act": (n_act,)}
+    return {n: Guarded(E, tails.get(n, ())) for n in OUT_NAMES}
+
+
+def _inputs(obs=None, prev=None):
+    """Guarded device copies of the CPU inputs: NaN guards (flags: set guards)."""
+    o = Guarded(obs.shape[0], obs.shape[1:], obs, NAN) if obs is not None else None
+    p = None
+    if prev is not None:
+        rew, te, tr, tobs = prev
+        E = rew.shape[0]
+        p = (Guarded(E, (), rew, NAN), Guarded(E, (), te, 1, torch.uint8), Guarded(E, (), tr, 1, torch.uint8),
+             Guarded(E, tobs.shape[1:], tobs, NAN))
+    return o, p
+
+
+def _call(k, outs, want, obs=None, prev=None, **kw):
+    """k.step with the outputs named in ``want``; then the guards of those, all of every other
+    output and all of every input are bit-unchanged."""
+    k.step(obs.t if obs is not None else None, prev=tuple(p.t for p in prev) if prev is not None else None,
+           **{n: outs[n].t for n in want}, **kw)
+    torch.cuda.synchronize()
+    for n, gd in outs.items():
+        assert gd.guards_intact() if n in want else gd.untouched(), n
+    for gd in ([obs] if obs is not None else []) + (list(prev) if prev is not None else []):
+        assert gd.untouched()
+
+
+def _gate(tag, got, want64, yard32):
+    """max and rms of kernel - float64 reference within 4 x those of the float32 reference."""
+    err = got.astype(np.float64) - want64
+    e_ref = yard32.astype(np.float64) - want64
+    mx, rms = np.abs(err).max(), math.sqrt(np.mean(err ** 2))
+    mx_ref, rms_ref = np.abs(e_ref).max(), math.sqrt(np.mean(e_ref ** 2))
+    print(f"GATE {tag}: max|e_ref| {mx_ref:.2e} rms {rms_ref:.2e}  kernel / e_ref: max "
+          f"{mx / mx_ref if mx_ref else math.inf:.2f} rms {rms / rms_ref if rms_ref else math.inf:.2f}")
+    assert not np.isnan(got).any(), tag
+    assert mx <= 4 * mx_ref and rms <= 4 * rms_ref, (tag, mx, mx_ref, rms, rms_ref)
+
+
+def _logp64(pol, act, mu):
+    ls = pol.log_std.detach().cpu().numpy().astype(np.float64)
+    act, mu = act.astype(np.float64), mu.astype(np.float64)
+    return (-((act - mu) ** 2) / (2 * np.exp(ls) ** 2) - ls - 0.5 * math.log(2 * math.pi)).sum(-1)
+
+
+def _check_forward(tag, pol, obs, outs, names):
+    """The deterministic outputs in ``names`` against forward64 of the CPU rows ``obs``."""
+    mu64, v64 = ref.forward64(pol, obs)
+    mu32, v32 = ref.forward32(pol, obs)
+    if "buf_act" in names:
+        _gate(tag + " mu", outs["buf_act"].np(), mu64, mu32)
+    if "buf_val" in names:
+        _gate(tag + " v", outs["buf_val"].np(), v64, v32)
+    if "buf_obs" in names:
+        assert torch.equal(_bits(outs["buf_obs"].t.cpu()), _bits(obs))
+    if "act_env" in names:
+        env = outs["act_env"].np()
+        if "buf_act" in names:
+            assert np.array_equal(env, np.clip(outs["buf_act"].np(), -1.0, 1.0))
+        # the clip is 1-Lipschitz: an action within the gate stays within it
+        err = env.astype(np.float64) - np.clip(mu64, -1.0, 1.0)
+        e_ref = mu32.astype(np.float64) - mu64
+        assert np.abs(err).max() <= 4 * np.abs(e_ref).max()
+        assert math.sqrt(np.mean(err ** 2)) <= 4 * math.sqrt(np.mean(e_ref ** 2))
+        assert np.abs(env).max() <= 1.0
+        assert (env[mu64 > 1.001] == 1.0).all() and (env[mu64 < -1.001] == -1.0).all()
+    if "buf_logp" in names:       # Normal(mu, std).log_prob(mu): tests/test_gpu_policy.py's gate
+        np.testing.assert_allclose(outs["buf_logp"].np(), _logp64(pol, mu64, mu64), rtol=1e-6, atol=1e-5)
+    return mu64
+
+
+def _check_prev(tag, pol, prev, outs, gamma):
+    rew, te, tr, tobs = prev
+    want, done, boot = ref.bootstrap64(pol, rew, te, tr, tobs, gamma)
+    yard, _, _ = ref.bootstrap32(pol, rew, te, tr, tobs, gamma)
+    got = outs["buf_rew"].np()
+    assert not np.isnan(got).any() and not np.isnan(outs["buf_done"].np()).any()
+    assert boot.any() and not boot.all()
+    assert np.array_equal(got[~boot].view(np.int32), rew.numpy()[~boot].view(np.int32))
+    _gate(tag + " rew", got[boot], want[boot], yard[boot])
+    assert np.array_equal(outs["buf_done"].np(), done)
+
+
+def _assert_clipped_both_sides(outs):
+    a, e = outs["buf_act"].np(), outs["act_env"].np()
+    assert (a > 1).any() and (a < -1).any()
+    assert (e[a > 1] == 1.0).all() and (e[a < -1] == -1.0).all()
+
+
+# ---- B1: every layer-1 register bucket, load path and action count
+SWEEP = [1, 9, 32, 54, 64, 70, 72, 73, 81, 96, 108, 141, 145, 191, 192]
+
+
+@pytest.mark.parametrize("n_obs,n_act", [(n, i % 8 + 1) for i, n in enumerate(SWEEP)] + [(27, 8)])
+def test_shape_sweep(n_obs, n_act):
+    """E = 37 (three groups, the last ragged), deterministic, every output, with the previous
+    step's bootstrap: groups 0 and 2 run forward<T,T,T>, group 1 forward<T,T,F>."""
+    from gym_pybullet_drones_routing_amd.policy import MlpPolicyKernel
+    E = 37
+    # (a one-wide input gives mu a one-parameter range: a module whose range crosses both -1 and 1)
+    pol = _module(n_obs, n_act, 113 if n_obs == 1 else 100 + n_obs)
+    k = MlpPolicyKernel(pol, seed=3)
+    obs = _rows(pol, E, n_obs, 1, True)
+    assert np.abs(ref.layer1_preact64(pol, obs)).max() > 4
+    prev = _prev(pol, E, n_obs, 2, 0.3)
+    og, pg = _inputs(obs, prev)
+    outs = _outputs(E, n_obs, n_act)
+    _call(k, outs, OUT_NAMES, og, pg, deterministic=True, gamma=0.97)
+    tag = f"sweep {n_obs}x{n_act}"
+    _check_forward(tag, pol, obs, outs, OUT_NAMES)
+    _assert_clipped_both_sides(outs)
+    _check_prev(tag, pol, prev, outs, 0.97)
+    assert not bool(k.rng[1:].any())          # deterministic calls draw nothing
+
+
+# ---- B2: the float2 and scalar fallbacks of the weight loads
+def _rebased(pol, residue):
+    """A copy of ``pol`` whose parameters are views into one flat buffer, each based ``residue``
+    bytes (4: 4-byte aligned only, 8: 8-byte aligned only) past a 16-byte boundary."""
+    import copy
+    cp = copy.deepcopy(pol)
+    params = list(cp.parameters())
+    flat = torch.zeros(sum(p.numel() + 8 for p in params) + 8, device="cuda")
+    o = 0
+    for p in params:
+        while (flat.data_ptr() + 4 * o) % 16 != residue:
+            o += 1
+        n = p.numel()
+        flat[o:o + n] = p.data.reshape(-1)
+        p.data = flat[o:o + n].view_as(p)
+        assert p.data_ptr() % 16 == residue and p.is_contiguous()
+        o += n
+    return cp, flat
+
+
+@pytest.mark.parametrize("residue", [4, 8])
+@pytest.mark.parametrize("n_obs,n_act", [(72, 4), (96, 2)])
+def test_misaligned_parameters(n_obs, n_act, residue):
+    """The fallbacks do the same arithmetic on the same values: bit-identical outputs."""
+    from gym_pybullet_drones_routing_amd.policy import MlpPolicyKernel
+    E = 37
+    pol = _module(n_obs, n_act, 7)
+    for p in pol.parameters():
+        assert p.data_ptr() % 16 == 0
+    pol2, _flat = _rebased(pol, residue)
+    for p, q in zip(pol.parameters(), pol2.parameters()):
+        assert torch.equal(p, q)
+    obs = _rows(pol, E, n_obs, 1, True)
+    prev = _prev(pol, E, n_obs, 2, 0.3)
+    res = []
+    for m in (pol, pol2):
+        og, pg = _inputs(obs, prev)
+        outs = _outputs(E, n_obs, n_act)
+        _call(MlpPolicyKernel(m, seed=3), outs, OUT_NAMES, og, pg, deterministic=True)
+        res.append(outs)
+    _check_forward(f"misaligned {n_obs}x{n_act}", pol, obs, res[0], OUT_NAMES)
+    for n in OUT_NAMES:
+        assert torch.equal(_bits(res[0][n].t), _bits(res[1][n].t)), n
+    # and the sampled path (exp(log_std) and the output weights are read from the rebased buffer too)
+    acts = []
+    for m in (pol, pol2):
+        og, _ = _inputs(obs)
+        outs = _outputs(E, n_obs, n_act)
+        _call(MlpPolicyKernel(m, seed=3), outs, ("buf_act", "buf_logp"), og)
+        acts.append(outs)
+    for n in ("buf_act", "buf_logp"):
+        assert torch.equal(_bits(acts[0][n].t), _bits(acts[1][n].t)), n
+
+
+# ---- B3: every forward<ACT, CRIT, BOOT> instantiation and partial output sets
+@pytest.mark.parametrize("n_obs,n_act", [(27, 3), (144, 6)])
+def test_modes(n_obs, n_act):
+    from gym_pybullet_drones_routing_amd.policy import MlpPolicyKernel
+    E = 53
+    pol = _module(n_obs, n_act, 11)
+    k = MlpPolicyKernel(pol, seed=SEED, max_rows=E + 5 * G)
+    obs = _rows(pol, E, n_obs, 3, True)
+    prev = _prev(pol, E, n_obs, 4, 0.3)
+    tag = f"modes {n_obs}x{n_act}"
+    rng0 = k.rng.clone()
+
+    # obs + every buffer + prev: forward<T,T,T> (groups 0, 2, 3) and <T,T,F> (group 1)
+    og, pg = _inputs(obs, prev)
+    outs = _outputs(E, n_obs, n_act)
+    _call(k, outs, OUT_NAMES, og, pg, deterministic=True, gamma=0.99)
+    mu64 = _check_forward(tag + " full", pol, obs, outs, OUT_NAMES)
+    _assert_clipped_both_sides(outs)
+    _check_prev(tag + " full", pol, prev, outs, 0.99)
+    mu_k = outs["buf_act"].np().copy()
+
+    # the critic only + prev (learn.py's last call of a rollout): forward<F,T,T> and <F,T,F>
+    outs = _outputs(E, n_obs, n_act)
+    _call(k, outs, ("buf_val", "buf_rew", "buf_done"), og, pg, gamma=0.99)
+    _check_forward(tag + " critic", pol, obs, outs, ("buf_val",))
+    _check_prev(tag + " critic", pol, prev, outs, 0.99)
+
+    # the bootstrap only: forward<F,F,T> in groups that hold a truncation, nothing in group 1
+    outs = _outputs(E, n_obs, n_act)
+    _call(k, outs, ("buf_rew", "buf_done"), None, pg, gamma=0.99)
+    _check_prev(tag + " boot", pol, prev, outs, 0.99)
+
+    # the actor with only act_env
+    outs = _outputs(E, n_obs, n_act)
+    _call(k, outs, ("act_env",), og, deterministic=True)
+    _check_forward(tag + " act_env", pol, obs, outs, ("act_env",))
+    assert np.array_equal(outs["act_env"].np(), np.clip(mu_k, -1.0, 1.0))
+    assert torch.equal(k.rng, rng0)           # nothing so far has sampled
+
+    # the actor with only buf_logp, sampled: the log-density of the action the same counters draw
+    # (a twin call that also writes buf_act), by tests/test_gpu_policy.py's gate
+    twin = _outputs(E, n_obs, n_act)
+    _call(k, twin, ("buf_act", "buf_logp"), og)
+    k.rng.copy_(rng0)
+    outs = _outputs(E, n_obs, n_act)
+    _call(k, outs, ("buf_logp",), og)
+    act = twin["buf_act"].np()
+    assert not np.isnan(act).any() and not np.array_equal(act, mu_k)
+    assert torch.equal(_bits(outs["buf_logp"].t), _bits(twin["buf_logp"].t))
+    np.testing.assert_allclose(outs["buf_logp"].np(), _logp64(pol, act, mu_k), rtol=1e-5, atol=2e-5)
+    groups = -(-E // G)
+    assert torch.equal(k.rng[2:2 + groups], rng0[2:2 + groups] + 1) and torch.equal(k.rng[2 + groups:], rng0[2 + groups:])
+    assert torch.equal(k.rng[:2], rng0[:2])
+    assert np.abs(mu64).max() > 1
+
+
+# ---- B4: the grid-stride loop
+BIG = 2 * 32768 + 5          # 2048 blocks x 16 rows, twice, and a ragged third trip of block 0
+
+
+@pytest.mark.parametrize("n_obs,n_act", [(27, 1), (144, 8)])
+def test_grid_stride(n_obs, n_act):
+    from gym_pybullet_drones_routing_amd.policy import MlpPolicyKernel
+    E = BIG
+    pol = _module(n_obs, n_act, 13)
+    k = MlpPolicyKernel(pol, seed=5, max_rows=E)
+    obs = _rows(pol, E, n_obs, 5, False)
+    prev = _prev(pol, E, n_obs, 6, 0.05)
+    og, pg = _inputs(obs, prev)
+    tag = f"stride {n_obs}x{n_act}"
+
+    boot = _outputs(E, 1, 1)                  # the bootstrap-only mode (its obs-wide outputs: unused)
+    _call(k, boot, ("buf_rew", "buf_done"), None, pg, gamma=0.99)
+    _check_prev(tag + " boot", pol, prev, boot, 0.99)
+    boot_rew = boot["buf_rew"].t.clone()
+    del boot
+
+    outs = _outputs(E, n_obs, n_act)
+    _call(k, outs, OUT_NAMES, og, pg, deterministic=True, gamma=0.99)
+    _check_forward(tag + " full", pol, obs, outs, OUT_NAMES)
+    _assert_clipped_both_sides(outs)
+    _check_prev(tag + " full", pol, prev, outs, 0.99)
+    # the bootstrap is the same instruction sequence in either mode
+    assert torch.equal(_bits(boot_rew), _bits(outs["buf_rew"].t))
+
+    # geometry independence: one slice of each trip (the ragged last one included) as a call of
+    # its own; every row's instruction sequence is the same in either geometry
+    for s, n in ((160, 48), (32768 + 1600, 37), (2 * 32768, 5)):
+        assert s % G == 0 and s + n <= E
+        sl = slice(s, s + n)
+        small = {nm: torch.full_like(outs[nm].t[sl], SENT) for nm in OUT_NAMES}
+        k.step(og.t[sl], prev=tuple(p.t[sl] for p in pg), deterministic=True, gamma=0.99, **small)
+        torch.cuda.synchronize()
+        for nm in OUT_NAMES:
+            assert torch.equal(_bits(small[nm]), _bits(outs[nm].t[sl])), (nm, s)
+        small = {nm: torch.full_like(outs[nm].t[sl], SENT) for nm in ("buf_rew", "buf_done")}
+        k.step(None, prev=tuple(p.t[sl] for p in pg), gamma=0.99, **small)
+        torch.cuda.synchronize()
+        for nm in small:
+            assert torch.equal(_bits(small[nm]), _bits(outs[nm].t[sl])), (nm, s)
+    assert not bool(k.rng[1:].any())
+
+
+# ---- B5: the exact random stream
+def _expect_sample(pol, mu_k, seed, calls, E, n_act):
+    """Expected sampled actions and their tolerance: mu_k + std_normal64 * exp(log_std)."""
+    rows = np.arange(E, dtype=np.uint64)[:, None]
+    a = np.arange(n_act, dtype=np.uint64)[None, :]
+    call = np.asarray(calls, dtype=np.uint64)[np.arange(E) // G][:, None]
+    eps, rad = ref.std_normal64(seed, call, rows, a, with_radius=True)
+    sc = np.exp(pol.log_std.detach().cpu().numpy().astype(np.float64))[None, :]
+    return mu_k.astype(np.float64) + eps * sc, sc * (8e-7 * rad + 3e-7 * np.abs(eps)), eps
+
+
+def _check_sample(tag, pol, outs, mu_k, seed, calls, E, n_act):
+    act = outs["buf_act"].np()
+    want, b, eps = _expect_sample(pol, mu_k, seed, calls, E, n_act)
+    err = np.abs(act.astype(np.float64) - want)
+    tol = 4 * b + 2 * U * np.abs(act)
+    print(f"SAMPLE {tag}: max err / tol {np.max(err / np.maximum(tol, 1e-300)):.3f}  max|eps| {np.abs(eps).max():.2f}")
+    assert not np.isnan(act).any()
+    assert (err <= tol).all(), (tag, float(err.max()), int(np.argmax(err - tol)))
+    assert np.array_equal(outs["act_env"].np(), np.clip(act, -1.0, 1.0))
+    np.testing.assert_allclose(outs["buf_logp"].np(), _logp64(pol, act, mu_k), rtol=1e-5, atol=2e-5)
+
+
+@pytest.mark.parametrize("n_obs,n_act,E", [(27, 1, 333), (54, 5, 333), (144, 8, 333), (144, 8, BIG)])
+def test_exact_random_stream(n_obs, n_act, E):
+    """A deterministic call gives the kernel's own mu_k (the sampling path computes the same mu),
+    which isolates the sampler.  Every row group has a counter of its own: group 0's low word is
+    ffffffff, every later group's high word is 1."""
+    from gym_pybullet_drones_routing_amd.policy import MlpPolicyKernel
+    pol = _module(n_obs, n_act, 17)
+    k = MlpPolicyKernel(pol, seed=SEED, max_rows=E + 10 * G)
+    groups, total = -(-E // G), k.rng_groups
+    assert total >= groups + 10
+    assert int(k.rng[0]) == SEED and int(k.rng[1]) == 0
+    k.rng[2:] = torch.arange(total, dtype=torch.int64, device="cuda") + (2 ** 32 - 1)
+    calls0 = np.arange(total, dtype=np.uint64) + np.uint64(2 ** 32 - 1)
+    rng0 = k.rng.clone()
+    obs = _rows(pol, E, n_obs, 7, False)
+    og, _ = _inputs(obs)
+    det = _outputs(E, n_obs, n_act)
+    _call(k, det, ("buf_act",), og, deterministic=True)
+    mu_k = det["buf_act"].np().copy()
+    assert torch.equal(k.rng, rng0)
+    del det
+    tag = f"stream {n_obs}x{n_act}x{E}"
+    for call_no in range(2):                  # the second call follows the advanced counters
+        outs = _outputs(E, n_obs, n_act)
+        _call(k, outs, ("act_env", "buf_act", "buf_logp"), og)
+        _check_sample(f"{tag} call {call_no}", pol, outs, mu_k, SEED, calls0 + np.uint64(call_no), E, n_act)
+        now = k.rng.cpu()
+        want = rng0.cpu().clone()
+        want[2:2 + groups] += call_no + 1     # every covered group up by exactly one per call
+        assert torch.equal(now, want)         # key, rng[1] and the counters beyond the batch unchanged
+        del outs
+
+
+def test_seed_is_taken_mod_2_64():
+    """A seed of 2^64 - 1 constructs, is stored as -1 and draws the stream of key (ffffffff, ffffffff)."""
+    from gym_pybullet_drones_routing_amd.policy import MlpPolicyKernel
+    n_obs, n_act, E = 54, 5, 37
+    pol = _module(n_obs, n_act, 19)
+    k = MlpPolicyKernel(pol, seed=2 ** 64 - 1, max_rows=E)
+    assert int(k.rng[0]) == -1 and k.calls == 0
+    assert int(MlpPolicyKernel(pol, seed=2 ** 63).rng[0]) == -2 ** 63
+    assert int(MlpPolicyKernel(pol, seed=-1).rng[0]) == -1
+    assert int(MlpPolicyKernel(pol, seed=2 ** 64 + 5).rng[0]) == 5
+    obs = _rows(pol, E, n_obs, 7, False)
+    og, _ = _inputs(obs)
+    det = _outputs(E, n_obs, n_act)
+    _call(k, det, ("buf_act",), og, deterministic=True)
+    outs = _outputs(E, n_obs, n_act)
+    _call(k, outs, ("act_env", "buf_act", "buf_logp"), og)
+    _check_sample("seed 2^64-1", pol, outs, det["buf_act"].np(), 2 ** 64 - 1, np.zeros(3, dtype=np.uint64), E, n_act)
+    assert k.calls == 1 and int(k.rng[0]) == -1
+
+
+# ---- B6: small edges
+@pytest.mark.parametrize("T,E", [(1, 1), (3, 257)])
+def test_gae_small_shapes(T, E):
+    """Bit-identical to examples/learn.py's loop, as tests/test_gpu_policy.py checks at (64, 4097)."""
+    from gym_pybullet_drones_routing_amd.policy import MlpPolicyKernel
+    k = MlpPolicyKernel(_module(27, 1, 1))
+    g = torch.Generator().manual_seed(8)
+    rew, val = torch.randn((T, E), generator=g).cuda(), torch.randn((T, E), generator=g).cuda()
+    done = (torch.rand((T, E), generator=g) < 0.3).float().cuda()
+    last_v = torch.randn(E, generator=g).cuda()
+    gamma, lam = 0.99, 0.95
+    adv_g, ret_g = Guarded(T, (E,)), Guarded(T, (E,))
+    k.gae(rew, val, done, last_v, gamma, lam, adv_g.t, ret_g.t)
+    adv = torch.zeros_like(rew)
+    gg = torch.zeros(E, device="cuda")
+    for t in reversed(range(T)):
+        nv = last_v if t == T - 1 else val[t + 1]
+        nonterm = 1.0 - done[t]
+        delta = rew[t] + gamma * nv * nonterm - val[t]
+        gg = delta + gamma * lam * nonterm * gg
+        adv[t] = gg
+    ret = adv + val
+    torch.cuda.synchronize()
+    assert torch.equal(adv_g.t, adv) and torch.equal(ret_g.t, ret)
+    assert adv_g.guards_intact() and ret_g.guards_intact()
+
+
+def test_error_paths_name_the_problem():
+    """Only ValueError and GpdError, each naming what is wrong; none launches anything."""
+    from gym_pybullet_drones_routing_amd._lib import GpdError
+    from gym_pybullet_drones_routing_amd.policy import MlpPolicyKernel
+    n_obs, n_act, E = 27, 2, 37
+    pol = _module(n_obs, n_act, 23)
+    k = MlpPolicyKernel(pol, seed=1, max_rows=E)
+    rng0 = k.rng.clone()
+    obs = _rows(pol, E, n_obs, 1, False)
+    prev = _prev(pol, E, n_obs, 2, 0.3)
+    og, pg = _inputs(obs, prev)
+    outs = _outputs(E, n_obs, n_act)
+    with pytest.raises(ValueError, match=rf"buf_val must hold {E} x 1 elements, has {E - 1}"):
+        k.step(og.t, buf_act=outs["buf_act"].t, buf_val=outs["buf_val"].t[:E - 1])
+    with pytest.raises(ValueError, match=rf"buf_act must hold {E - 1} x {n_act} elements"):
+        k.step(og.t[:E - 1], buf_act=outs["buf_act"].t)
+    with pytest.raises(ValueError, match=rf"obs must hold {E + 1} x {n_obs} elements"):
+        k.step(og.t, buf_act=outs["buf_act"].t, n_rows=E + 1)
+    wide = torch.full((E, 2 * n_act), SENT, device="cuda")
+    with pytest.raises(ValueError, match="buf_act must be a contiguous float32"):
+        k.step(og.t, buf_act=wide[:, :n_act])
+    f64 = torch.full((E,), SENT, dtype=torch.float64, device="cuda")
+    with pytest.raises(ValueError, match="buf_val must be a contiguous float32"):
+        k.step(og.t, buf_val=f64)
+    with pytest.raises(GpdError, match="buf_rew") as ei:
+        k.step(og.t, buf_val=outs["buf_val"].t, prev=tuple(p.t for p in pg), buf_done=outs["buf_done"].t)
+    assert ei.value.code == -1
+    big = _rows(pol, E + G, n_obs, 3, False).cuda()
+    scratch = torch.zeros(4, device="cuda")
+    big_env = torch.full((E + G, n_act), SENT, device="cuda")
+    torch.cuda.synchronize()
+    gr = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(gr):
+        scratch.add_(1.0)                      # (the capture holds something whatever comes next)
+        with pytest.raises(ValueError, match="before capturing a graph"):
+            k.step(big, act_env=big_env)       # more rows than the counters cover
+    torch.cuda.synchronize()
+    assert bool((big_env == SENT).all()) and bool((scratch == 0).all())
+    assert k.rng_groups == -(-E // G) and torch.equal(k.rng, rng0)
+    assert bool((wide == SENT).all()) and bool((f64 == SENT).all())
+    for gd in outs.values():
+        assert gd.untouched()
