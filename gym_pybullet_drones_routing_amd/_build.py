@@ -11,7 +11,8 @@ PKG_DIR = pathlib.Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 LIB_PATH = PKG_DIR / "libgpd.so"
-SOURCES = [CSRC / "gpd.hip", CSRC / "gpd_kernels.h", CSRC / "gpd_device.h", CSRC / "gpd_ctrl.h", CSRC / "gpd_handoff.h", INCLUDE / "gpd.h"]
+# every header and source under csrc/: a header added later cannot be missed by needs_build()
+SOURCES = sorted(CSRC.glob("*.h")) + sorted(CSRC.glob("*.hip")) + [INCLUDE / "gpd.h"]
 ARCH = os.environ.get("GPD_OFFLOAD_ARCH", "gfx950")
 
 

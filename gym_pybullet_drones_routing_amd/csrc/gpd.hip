@@ -193,7 +193,7 @@ Consts<R> make_consts(const gpd_sim* s) {
   c.plane_half = (R)15.0;    // plane.urdf collision box 30 x 30
   c.resid = (R)1e-7;         // m_leastSquaresResidualThreshold (pybullet)
   {
-    // drone <-> drone contact (drone_contact, gpd_kernels.h; oracle/bullet_mb.py drone_contact)
+    // drone <-> drone contact (drone_contact, gpd_dcontact.h; oracle/bullet_mb.py drone_contact)
     const double bs = std::sqrt(P.collision_r * P.collision_r + (P.collision_h / 2) * (P.collision_h / 2));
     const double reach = 2.0 * bs + (double)c.brk;
     c.dd_reach2 = (R)(reach * reach);
@@ -203,9 +203,6 @@ Consts<R> make_consts(const gpd_sim* s) {
   // setPhysicsEngineParameter(numSolverIterations=, solverResidualThreshold=) (gpd_config)
   if (s->cfg.solver_iterations > 0) c.iters = s->cfg.solver_iterations;
   if (s->cfg.solver_residual != 0.0) c.resid = (R)s->cfg.solver_residual;
-#ifdef GPD_DIAG_RESID
-  c.resid = (R)GPD_DIAG_RESID;   // diagnostic builds only (e.g. -1: every solve runs c.iters iterations)
-#endif
   c.nsub = s->nsub;
   const gpd_pid_params& Q = s->pid;
   PidConsts<R>& k = c.pid;
@@ -801,7 +798,7 @@ int gpd_create(const gpd_drone_params* params, const gpd_config* cfg, gpd_sim** 
     return fail(GPD_ENOMEM, "gpd_create: hipMalloc failed");
   }
   if ((C.physics_flags & GPD_F_BULLET) && s->D > 1 && !(C.physics_flags & GPD_F_NO_DRONE_CONTACT)) {
-    // drone <-> drone contact (gpd_kernels.h DcHook / dc_solve): the pair table of an env and the
+    // drone <-> drone contact (gpd_dcontact.h DcHook / dc_solve): the pair table of an env and the
     // row store for a block's contacts past its first 64 (up to kDcPts per pair: the closest point
     // and the face manifold)
     const int D = s->D, P = D * (D - 1) / 2;

@@ -17,14 +17,7 @@ namespace gpd {
 // ---------------------------------------------------------------- precision-overloaded math
 // A wave-uniform branch that practically never runs: laid out after the hot path, so its code
 // is not fetched into the instruction cache on the launches that skip it.
-#if defined(GPD_NOCOLD)
-#define GPD_RARE(x) ((x) && false)   // diagnostic build: every rare branch compiled out (bounds the
-                                     // instruction-cache gain of moving them out of line)
-#elif defined(GPD_NOEXPECT)
-#define GPD_RARE(x) (x)
-#else
 #define GPD_RARE(x) __builtin_expect((x), 0)
-#endif
 __device__ __forceinline__ float g_sqrt(float x) { return sqrtf(x); }
 __device__ __forceinline__ double g_sqrt(double x) { return sqrt(x); }
 __device__ __forceinline__ float g_sin(float x) { return sinf(x); }
@@ -209,13 +202,11 @@ __device__ __forceinline__ DynK<R> dyn_consts(const Consts<R>& c, int warm0 = 0,
   // one statement for all of them: hipcc issues the scalar loads of every constant-block line
   // back to back and waits once (K$ misses in parallel), instead of a load + wait pair per use
   // behind each model / flag branch
-#ifndef GPD_NO_DYNK_PIN
   asm volatile("" : "+v"(k.dt), "+v"(k.inv_m), "+v"(k.gravity), "+v"(k.jx), "+v"(k.jy), "+v"(k.jz),
                "+v"(k.ijx), "+v"(k.ijy), "+v"(k.ijz), "+v"(k.hdt), "+v"(k.hdt2), "+v"(k.kf), "+v"(k.km),
                "+v"(k.L), "+v"(k.Ls2), "+v"(k.hover_f32), "+s"(k.model), "+s"(k.flags),
                "+s"(k.nsub)
                : "s"(warm0), "s"(warm1));
-#endif
   return k;
 }
 
@@ -496,18 +487,11 @@ __device__ __forceinline__ bool upright(const AttitudeArgs<R>& t) {
 }
 
 // ---------------------------------------------------------------- cold paths out of line
-// GPD_COLD_CALLS=1: the rare branches' bodies (the library cos / sin of the _integrateQ weights for
-// |theta| >= 0.5, the exact attitude re-decision) become calls, so their code sits outside the
-// kernel's instruction stream instead of after its end (instruction fetch).
-// Measured: headline kernel 4.97 us vs 5.03-5.34 us inline (profiles/r4/cold/); 0 = inline.
-#ifndef GPD_COLD_CALLS
-#define GPD_COLD_CALLS 1
-#endif
-#if GPD_COLD_CALLS
+// The rare branches' bodies (the library cos / sin of the _integrateQ weights for |theta| >= 0.5,
+// the exact attitude re-decision) are calls, so their code sits outside the kernel's instruction
+// stream instead of after its end (instruction fetch).
+// Measured: headline kernel 4.97 us vs 5.03-5.34 us inline (profiles/r4/cold/).
 #define GPD_COLD __attribute__((noinline, cold))
-#else
-#define GPD_COLD __forceinline__
-#endif
 template <typename R>
 struct CoSh {
   R co, sh;
@@ -606,13 +590,9 @@ __device__ __forceinline__ void attitude_decide(R qx, R qy, R qz, R qw, Attitude
 // float32 Euler angles for the float32 observation.  The reference computes them in float64
 // (pybullet's getEulerFromQuaternion, BaseAviary.py:518) and casts them (BaseRLAviary.py:313-315).
 // Here they are float32 asinf / atan2f of the double arguments (within ~2 float32 ulp of the cast
-// double result).  GPD_OBS_ANGLES_F64=1 builds the reference's order - double asin / atan2, then
-// the cast - and was measured on the 4096-env headline kernel (budget 0.1 us):
-// 5.01-5.04 -> 5.41-5.73 us per launch (three alternations, profiles/r4/angles/), ~2 KB more code
-// in the epilogue; not the default.
-#ifndef GPD_OBS_ANGLES_F64
-#define GPD_OBS_ANGLES_F64 0
-#endif
+// double result).  The reference's order - double asin / atan2, then the cast - was measured on
+// the 4096-env headline kernel (budget 0.1 us): 5.01-5.04 -> 5.41-5.73 us per
+// launch (three alternations, profiles/r4/angles/), ~2 KB more code in the epilogue; not kept.
 template <typename R>
 __device__ __forceinline__ void obs_euler_f32(const R q[4], const AttitudeArgs<R>& t, float& roll, float& pitch,
                                               float& yaw) {
@@ -620,15 +600,9 @@ __device__ __forceinline__ void obs_euler_f32(const R q[4], const AttitudeArgs<R
   // the regular branch for every lane, the gimbal branches (|sarg| >= 0.99999) as a
   // wave-uniform fix-up
   const R sa = t.sarg < R(-1) ? R(-1) : (t.sarg > R(1) ? R(1) : t.sarg);
-  if (GPD_OBS_ANGLES_F64 && sizeof(R) == 8) {
-    pitch = (float)g_asin(sa);
-    roll = (float)g_atan2(t.a, t.b);
-    yaw = (float)g_atan2(R(2) * (x * y + w * z), w * w + x * x - y * y - z * z);
-  } else {
-    pitch = asinf((float)sa);
-    roll = atan2f((float)t.a, (float)t.b);
-    yaw = atan2f((float)(R(2) * (x * y + w * z)), (float)(w * w + x * x - y * y - z * z));
-  }
+  pitch = asinf((float)sa);
+  roll = atan2f((float)t.a, (float)t.b);
+  yaw = atan2f((float)(R(2) * (x * y + w * z)), (float)(w * w + x * x - y * y - z * z));
   if (GPD_RARE(__ballot(t.gimbal) != 0ull)) {
     if (t.sarg <= R(-0.99999)) {
       pitch = -1.57079632679489661923f; roll = 0.0f; yaw = (float)(R(2) * g_atan2(x, -y));
@@ -933,10 +907,8 @@ __device__ __forceinline__ void plane_contact(Drone<R>& s, const R Rm[9], const 
 // per-iteration instruction count is what the PYB step time follows.  PK's park() / unpark()
 // run after the setup and after the iterations: the caller moves what it keeps across the solve
 // out of VGPRs for the iterations (bullet_substep).
-#ifndef GPD_CONTACT_PARK
-#define GPD_CONTACT_PARK 1   // 0: diagnostic builds (A/B of the parking)
-#endif
-// kStage: the drone <-> drone solve stages its sweeps' operands in LDS (gpd_kernels.h DcStage) -
+// (The parking's A/B: DESIGN.md §4, profiles/r3/contact2/r3u_ab.log.)
+// kStage: the drone <-> drone solve stages its sweeps' operands in LDS (gpd_dcontact.h DcStage) -
 // the parking callers are the compiled-in PYB flag-set kernels, whose LDS has the room
 struct NoPark {
   static constexpr bool kStage = false;
@@ -1137,7 +1109,7 @@ __device__ __forceinline__ R contact_low(const Drone<R>& s, const R Rm[9], const
 // Bullet's two-term expansion to ~1e-30).
 // rpm / W / last / k are the caller's loop-carried values: a contact solve parks them in LDS and
 // hands back the reloaded copies (see the contact block below).
-// HK: the drone <-> drone contact of multi-drone envs (gpd_kernels.h DcHook), run on the
+// HK: the drone <-> drone contact of multi-drone envs (gpd_dcontact.h DcHook), run on the
 // unconstrained velocities before the ground-plane solve; NoDc elsewhere.
 struct NoDc {
   template <typename R, class PK>
@@ -1254,11 +1226,7 @@ __device__ __forceinline__ void bullet_substep(Drone<R>& s, R rpm[4], R W[4], R 
       // combination, whose kernels also serve non-contact configs) keep the LDS rows
       if (GPD_RARE(__ballot(low) != 0ull)) {
         if (PF != kPfRuntime) {
-#if GPD_CONTACT_PARK
           plane_contact_regs<R>(s, Rm, c, k, ParkFns<decltype(park), decltype(unpark)>{park, unpark}, island);
-#else
-          plane_contact_regs<R>(s, Rm, c, k, NoPark(), island);
-#endif
         } else {
           plane_contact<R>(s, Rm, c, k, island);
         }

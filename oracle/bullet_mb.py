@@ -331,7 +331,7 @@ RIM_SAME = 1e-4             # starts whose squared distances agree to this fract
 PAIR_TIE = 1e-7             # candidates within this of the closest count as tied: the first wins (m); sized
                             # for the f32 kernel (a level side-by-side pair ties its lateral line and both rims)
 # k * 22.5 deg: the first quadrant's (cos, sin) rotated by quarter turns, negations as 0 - x (no -0.0),
-# exactly as gpd_kernels.h np_rim_task forms them
+# exactly as gpd_narrowphase.h np_rim_task forms them
 _C1, _S1 = 0.92387953251128674, 0.38268343236508978      # cos / sin 22.5 deg
 _QC, _QS = (1.0, _C1, SIMDSQRT12, _S1), (0.0, _S1, SIMDSQRT12, _C1)
 RIM_COS = tuple((_QC[q], 0.0 - _QS[q], 0.0 - _QC[q], _QS[q])[k] for k in range(4) for q in range(4))

@@ -1,7 +1,7 @@
 """Drone <-> drone contact under Physics.PYB* (envs of several drones), GPU vs the oracle.
 
 MultiHoverAviary's drones are colliding Bullet bodies (BaseAviary.py:486-491, stepped together by
-p.stepSimulation at :369-370).  The restatement (oracle/bullet_mb.py drone_contact, gpd_kernels.h
+p.stepSimulation at :369-370).  The restatement (oracle/bullet_mb.py drone_contact, gpd_dcontact.h
 drone_contact) is this repository's own contact set and solver order: parity unpinned against
 pybullet, like the ground-plane contact.  These tests pin the HIP path to the oracle:
   * resynced substeps (integrate kernel, run-time flags) over head-on, glancing, stacked, tilted,

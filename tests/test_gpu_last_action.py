@@ -1,5 +1,5 @@
 """last_clipped_action (state[16:20], BaseAviary.py:372 / :466) when the step kernels leave it in
-the action ring (RPM action types without drag, csrc/gpd_kernels.h store_drone_step): every way
+the action ring (RPM action types without drag, csrc/gpd_layout.h store_drone_step): every way
 of reading or replacing it must see exactly what the reference holds.
 
   * after steps: action_to_rpm of the newest action, bit-exact against the oracle;

@@ -1,5 +1,5 @@
 """Envs of more than 64 drones (MultiHoverAviary(num_drones=D) with D in 65..1024): the
-multi-wave-workgroup kernels step_kernel_wide / integrate_kernel_wide (csrc/gpd_kernels.h),
+multi-wave-workgroup kernels step_kernel_wide / integrate_kernel_wide (csrc/gpd_step_wide.h),
 through the C ABI, against the C fp64 restatement (oracle/gpd_oracle.c, downwash O(D^2) as
 BaseAviary._downwash :785-811) and, for the PID and Physics.PYB paths, the numpy oracle.
 
