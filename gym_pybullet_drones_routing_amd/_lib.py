@@ -28,6 +28,7 @@ GPD_TASK_NONE, GPD_TASK_HOVER, GPD_TASK_MULTIHOVER = 0, 1, 2
 GPD_F_GND, GPD_F_DRAG, GPD_F_DW, GPD_F_GEOM_WRENCH, GPD_F_BULLET, GPD_F_NO_PLANE = 1, 2, 4, 8, 16, 32
 GPD_F_NO_DRONE_CONTACT = 64
 GPD_F32, GPD_F64 = 0, 1
+GPD_CMD_RPM, GPD_CMD_VEL, GPD_CMD_WAYPOINT = 0, 1, 2
 
 # Every symbol include/gpd.h declares (checked by tests/test_lib_symbols.py).
 EXPORTED = ("gpd_abi_version", "gpd_last_error", "gpd_default_params", "gpd_create", "gpd_destroy",
@@ -35,7 +36,7 @@ EXPORTED = ("gpd_abi_version", "gpd_last_error", "gpd_default_params", "gpd_crea
             "gpd_get_raw_state", "gpd_set_raw_state", "gpd_get_step_counters",
             "gpd_set_step_counters", "gpd_state_bytes", "gpd_save_state", "gpd_load_state",
             "gpd_default_pid_params", "gpd_set_pid_params", "gpd_get_ctrl_state", "gpd_set_ctrl_state",
-            "gpd_nonfinite", "gpd_pack_layout_of", "gpd_handoff_pack", "gpd_handoff_unpack")
+            "gpd_nonfinite", "gpd_cmd_step", "gpd_adjacency", "gpd_pack_layout_of", "gpd_handoff_pack", "gpd_handoff_unpack")
 
 
 class GpdLibraryError(RuntimeError):
@@ -129,6 +130,8 @@ def load():
         "gpd_get_ctrl_state": (ci, [vp, vp, vp]),
         "gpd_set_ctrl_state": (ci, [vp, vp, vp]),
         "gpd_nonfinite": (ci, [vp, vp, vp]),
+        "gpd_cmd_step": (ci, [vp, i, vp, vp, vp]),
+        "gpd_adjacency": (ci, [vp, ctypes.c_double, vp, vp]),
         "gpd_pack_layout_of": (ci, [i, i, i, ctypes.POINTER(PackLayout)]),
         "gpd_handoff_pack": (ci, [vp, ctypes.POINTER(PackLayout), vp]),
         "gpd_handoff_unpack": (ci, [vp, i, ctypes.c_longlong, ctypes.POINTER(PackLayout), vp, vp, vp, vp, vp, vp]),

@@ -24,6 +24,8 @@ using namespace gpd;
 static_assert(GPD_ACT_RPM == ACT_RPM && GPD_ACT_ONE_D_RPM == ACT_ONE_D_RPM && GPD_ACT_PID == ACT_PID &&
                   GPD_ACT_VEL == ACT_VEL && GPD_ACT_ONE_D_PID == ACT_ONE_D_PID,
               "action type codes of gpd.h and the kernels must agree");
+static_assert(GPD_CMD_RPM == CMD_RPM && GPD_CMD_VEL == CMD_VEL && GPD_CMD_WAYPOINT == CMD_WAYPOINT,
+              "command mode codes of gpd.h and the kernels must agree");
 constexpr int kCtrlComps = 9;
 constexpr size_t kLdsBytes = 160 * 1024;   // LDS per workgroup on gfx950
 
@@ -455,6 +457,55 @@ int launch_integrate(gpd_sim* s, const void* rpm, int n_sub, void* traj, hipStre
   }
   void* args[] = {(void*)&v, (void*)&c, (void*)&r, (void*)&n_sub, (void*)&tr};
   HIP_TRY(hipLaunchKernel(f, dim3(grid), dim3(kWave), args, 0, st));
+  HIP_TRY(hipGetLastError());
+  return GPD_OK;
+}
+
+// gpd_cmd_step.  Instantiations: the RPM mode on plain DYN and on the run-time flags, the
+// controller modes on the run-time flags only (every one that carries the contact code is
+// expensive to compile).
+template <typename R>
+const void* cmd_step_fn(bool multi, bool plain, bool ctrl) {
+  if (ctrl)
+    return multi ? (const void*)cmd_step_kernel<R, true, kPfRuntime, true>
+                 : (const void*)cmd_step_kernel<R, false, kPfRuntime, true>;
+  if (multi)
+    return plain ? (const void*)cmd_step_kernel<R, true, 0, false>
+                 : (const void*)cmd_step_kernel<R, true, kPfRuntime, false>;
+  return plain ? (const void*)cmd_step_kernel<R, false, 0, false>
+               : (const void*)cmd_step_kernel<R, false, kPfRuntime, false>;
+}
+template <typename R, int MAXT>
+const void* cmd_step_wide_fn(bool ctrl) {
+  return ctrl ? (const void*)cmd_step_kernel_wide<R, MAXT, true> : (const void*)cmd_step_kernel_wide<R, MAXT, false>;
+}
+
+template <typename R>
+int launch_cmd_step(gpd_sim* s, int mode, const void* actions, void* obs20, hipStream_t st) {
+  // (no settle_last launch: a pending last-action-in-the-ring mark belongs to a sim without drag,
+  // where the step reads no last_clipped_action; the kernel replaces the value and clears the mark)
+  const SimView<R> v = make_view<R>(s);
+  const Consts<R>* c = (const Consts<R>*)s->d_consts;
+  const bool ctrl = mode != GPD_CMD_RPM;
+  R max_rpm = (R)s->K.max_rpm;
+  R* o = (R*)obs20;
+  void* args[] = {(void*)&v, (void*)&c, (void*)&actions, (void*)&mode, (void*)&max_rpm, (void*)&o};
+  if (s->D > kWave) {
+    const void* fw = s->D <= 256 ? cmd_step_wide_fn<R, 256>(ctrl)
+                     : (s->D <= 512 ? cmd_step_wide_fn<R, 512>(ctrl) : cmd_step_wide_fn<R, 1024>(ctrl));
+    HIP_TRY(hipLaunchKernel(fw, dim3(s->E), dim3((s->D + kWave - 1) / kWave * kWave), args, 0, st));
+    return GPD_OK;
+  }
+  const void* f = cmd_step_fn<R>(s->D > 1, s->cfg.physics_flags == 0, ctrl);
+  HIP_TRY(hipLaunchKernel(f, dim3(grid_for(s->N, s->tpb)), dim3(kWave), args, 0, st));
+  return GPD_OK;
+}
+
+template <typename R>
+int launch_adjacency(gpd_sim* s, double radius, uint8_t* out, hipStream_t st) {
+  const SimView<R> v = make_view<R>(s);
+  const long long total = (long long)s->N * s->D;
+  hipLaunchKernelGGL((adjacency_kernel<R>), dim3(grid_for(total, 256)), dim3(256), 0, st, v, radius, out);
   HIP_TRY(hipGetLastError());
   return GPD_OK;
 }
@@ -907,6 +958,33 @@ int gpd_integrate(gpd_sim* sim, const void* rpm, int n_sub, void* traj, void* st
   hipStream_t st = (hipStream_t)stream;
   return sim->prec == GPD_F64 ? launch_integrate<double>(sim, rpm, n_sub, traj, st)
                               : launch_integrate<float>(sim, rpm, n_sub, traj, st);
+}
+
+int gpd_cmd_step(gpd_sim* sim, int mode, const void* actions, void* obs20, void* stream) {
+  if (mode != GPD_CMD_RPM && mode != GPD_CMD_VEL && mode != GPD_CMD_WAYPOINT)
+    return fail(GPD_EINVAL, "gpd_cmd_step: unknown mode " + std::to_string(mode) +
+                                " (GPD_CMD_RPM, GPD_CMD_VEL or GPD_CMD_WAYPOINT)");
+  if (!sim) return fail(GPD_EINVAL, "gpd_cmd_step: NULL sim");
+  if (!actions) return fail(GPD_EINVAL, "gpd_cmd_step: NULL actions");
+  if (mode != GPD_CMD_RPM && !sim->d_ctrl)
+    return fail(GPD_EINVAL, "gpd_cmd_step: the VEL and WAYPOINT modes run DSLPIDControl, and the sim's action type "
+                            "has no controller (create it with a PID action type)");
+  // RPM and VEL rows are loaded as 16-byte vectors, the state20 rows stored as such
+  if (mode != GPD_CMD_WAYPOINT && !aligned16(actions))
+    return fail(GPD_EINVAL, "gpd_cmd_step: actions must be 16-byte aligned");
+  if (obs20 && !aligned16(obs20)) return fail(GPD_EINVAL, "gpd_cmd_step: obs20 must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  return sim->prec == GPD_F64 ? launch_cmd_step<double>(sim, mode, actions, obs20, st)
+                              : launch_cmd_step<float>(sim, mode, actions, obs20, st);
+}
+
+int gpd_adjacency(gpd_sim* sim, double radius, uint8_t* out, void* stream) {
+  if (!sim) return fail(GPD_EINVAL, "gpd_adjacency: NULL sim");
+  if (!out) return fail(GPD_EINVAL, "gpd_adjacency: NULL out");
+  if (std::isnan(radius)) return fail(GPD_EINVAL, "gpd_adjacency: radius is NaN");
+  hipStream_t st = (hipStream_t)stream;
+  return sim->prec == GPD_F64 ? launch_adjacency<double>(sim, radius, out, st)
+                              : launch_adjacency<float>(sim, radius, out, st);
 }
 
 int gpd_get_state20(gpd_sim* sim, void* out, void* stream) {

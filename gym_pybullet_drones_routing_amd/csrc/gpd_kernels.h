@@ -36,3 +36,4 @@
 #include "gpd_step.h"
 #include "gpd_step_duo.h"
 #include "gpd_step_wide.h"
+#include "gpd_step_cmd.h"

@@ -219,7 +219,10 @@ __device__ __forceinline__ void store_drone_step(const SimView<R>& v, long long 
   }
 }
 
-// drone 0's lane of a step launch: the state's last_clipped_action columns are stale from here on
+// drone 0's lane of a step launch: the state's last_clipped_action columns are stale from here on.
+// ctr[E] has a second writer: the command step (unmark_last_in_ring, gpd_step_cmd.h) stores the
+// columns itself and clears the mark in-kernel, relying on the same invariant as this one: the mark
+// is only ever set on sims whose steps read no last_clipped_action (wt bit 2: RPM types, no drag).
 template <typename R>
 __device__ __forceinline__ void mark_last_in_ring(const SimView<R>& v, long long n) {
   if ((v.wt & 4) && n == 0) v.ctr[v.N / v.D] = make_int2(1, 0);

@@ -1,0 +1,256 @@
+// gpd_step_cmd.h — the command step (gpd_cmd_step): one env.step() of the reference's CtrlAviary /
+// VelocityAviary for every env in one launch, and the adjacency helper (gpd_adjacency).
+//   CMD_RPM       CtrlAviary._preprocessAction (envs/CtrlAviary.py:140): np.clip(a, 0, MAX_RPM)
+//   CMD_VEL       VelocityAviary._preprocessAction (envs/VelocityAviary.py:148-168), the VEL branch
+//                 of BaseRLAviary (:208-223) line for line
+//   CMD_WAYPOINT  DSLPIDControl.computeControl(target_pos, target_rpy=(0, 0, yaw), target_vel) on the
+//                 state of the last readback: the control loop of examples/pid.py on the device
+// then PYB_STEPS_PER_CTRL substeps on those RPMs (BaseAviary.py:343-372), the final readback and
+// the 20-float state vectors (_getDroneStateVector :541-561) as the observation.  No reward, no
+// done flag, no auto-reset, and the action ring of the RL step is left alone.
+// Needs substep_block (gpd_step.h) and wide_downwash (gpd_step_wide.h).
+#pragma once
+#include "gpd_step_wide.h"
+
+namespace gpd {
+
+enum : int { CMD_RPM = 0, CMD_VEL = 1, CMD_WAYPOINT = 2 };
+
+// The command of one drone -> its four RPMs.  CTRL: the controller modes (VEL / WAYPOINT; cs is the
+// drone's controller state, updated in place), else RPM.  `mode` is wave-uniform.
+// actions: RPM real [N][4] (the sim's precision: float64 controller outputs lose nothing),
+// VEL float [N][4], WAYPOINT real [N][7] = target_pos(3) target_yaw target_vel(3).
+template <typename R, bool CTRL>
+__device__ __forceinline__ void cmd_to_rpm(const Consts<R>& c, int mode, const void* __restrict__ actions, long long n,
+                                           R max_rpm, const Drone<R>& s, R cs[9], R rpm[4]) {
+  if (!CTRL) {
+    const R* src = (const R*)actions + n * 4;
+    typedef double gpd_d2 __attribute__((ext_vector_type(2)));
+    typedef float gpd_f4 __attribute__((ext_vector_type(4)));
+    R a[4];
+    if (sizeof(R) == 8) {   // a drone's row is one aligned 32-byte run (host-checked)
+      const gpd_d2 lo = reinterpret_cast<const gpd_d2*>(src)[0], hi = reinterpret_cast<const gpd_d2*>(src)[1];
+      a[0] = (R)lo.x; a[1] = (R)lo.y; a[2] = (R)hi.x; a[3] = (R)hi.y;
+    } else {
+      const gpd_f4 q = *reinterpret_cast<const gpd_f4*>(src);
+      a[0] = (R)q.x; a[1] = (R)q.y; a[2] = (R)q.z; a[3] = (R)q.w;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) rpm[k] = np_clip(a[k], R(0), max_rpm);
+  } else {
+    R qn[4], Rm[9], rpy[3];
+    readback_fused(s.qx, s.qy, s.qz, s.qw, qn, Rm);
+    quat_to_euler(qn, rpy[0], rpy[1], rpy[2]);
+    const R pos[3] = {s.px, s.py, s.pz}, vel[3] = {s.vx, s.vy, s.vz};
+    R tpos[3], tvel[3], tyaw;
+    if (mode == CMD_VEL) {
+      const float4 q = *reinterpret_cast<const float4*>((const float*)actions + n * 4);
+      const float a[4] = {q.x, q.y, q.z, q.w};
+      pid_targets<R, ACT_VEL>(c.pid, a, pos, rpy, tpos, tyaw, tvel);
+    } else {
+      const R* w = (const R*)actions + n * 7;
+      tpos[0] = w[0]; tpos[1] = w[1]; tpos[2] = w[2];
+      tyaw = w[3];
+      tvel[0] = w[4]; tvel[1] = w[5]; tvel[2] = w[6];
+    }
+    dsl_pid<R, false>(c.pid, pos, Rm, rpy, vel, tpos, tyaw, tvel, cs, rpm);
+  }
+}
+
+// The 20-float state vector of a drone after the step's last readback (the literal Bullet
+// readback of state20_kernel: exact gimbal branches).
+template <typename R>
+__device__ __forceinline__ void state20_row(const Drone<R>& s, const R last[4], R o[20]) {
+  R qn[4], roll, pitch, yaw;
+  quat_readback(s.qx, s.qy, s.qz, s.qw, qn);
+  quat_to_euler(qn, roll, pitch, yaw);
+  o[0] = s.px; o[1] = s.py; o[2] = s.pz;
+  o[3] = qn[0]; o[4] = qn[1]; o[5] = qn[2]; o[6] = qn[3];
+  o[7] = roll; o[8] = pitch; o[9] = yaw;
+  o[10] = s.vx; o[11] = s.vy; o[12] = s.vz;
+  o[13] = s.ax; o[14] = s.ay; o[15] = s.az;
+  o[16] = last[0]; o[17] = last[1]; o[18] = last[2]; o[19] = last[3];
+}
+
+// Copy-out of a one-wave block's state20 rows: the rows are [nact][20] reals, contiguous in HBM
+// and a multiple of 16 bytes long, staged column-major in LDS (tile[col][lane], kPad apart: the
+// lanes' writes and the transposed reads are bank-conflict free) and streamed out with
+// coalesced 16-byte stores (2 doubles / 4 floats, never across a row: 20 is a multiple of both).
+// Measured against every lane storing its own row (20 scalar stores at a 160-byte stride), on the
+// build that still launched settle_last in front of this kernel (not the shipped 10.9 / 14.5 us
+// one): the same at 4096 envs, 18.2 vs 19.6 us per step at 65536
+// (profiles/cmd_step/probe_settle_launch_rowlane_ab.txt).
+template <typename R>
+__device__ __forceinline__ void rows20_copy_out(const R* tile, int lane, int nact, R* __restrict__ dst) {
+  constexpr int G = 16 / (int)sizeof(R);
+  typedef R gpd_vec __attribute__((ext_vector_type(G)));
+  const int total = nact * (20 / G);
+#pragma unroll 2
+  for (int i = lane; i < total; i += kWave) {
+    const int el = i * G, row = el / 20, col = el - row * 20;
+    gpd_vec q;
+#pragma unroll
+    for (int g = 0; g < G; ++g) q[g] = tile[(col + g) * kPad + row];
+    reinterpret_cast<gpd_vec*>(dst)[i] = q;
+  }
+}
+
+// The command step stores last_clipped_action into the state itself, so it takes back the mark an
+// RL step may have left (mark_last_in_ring: "state[16..19] is stale, the value is in the ring").
+// Such sims have no drag (SimView::wt bit 2), so nothing in this step reads the stale columns, and
+// no block reads the mark: drone 0's lane clears it, as drone 0's lane of the RL step sets it.
+template <typename R>
+__device__ __forceinline__ void unmark_last_in_ring(const SimView<R>& v, long long n) {
+  if ((v.wt & 4) && n == 0) v.ctr[v.N / v.D] = make_int2(0, 0);
+}
+
+// ---------------------------------------------------------------------------------------
+// gpd_cmd_step for envs of up to 64 drones: one wave per block, the geometry of integrate_kernel
+// (whole envs per block, v.tpb drones), one control step as step_kernel runs it.
+// PF: 0 (plain DYN) or kPfRuntime; CTRL: the instantiation runs the controller (VEL / WAYPOINT).
+template <typename R, bool MULTI, int PF, bool CTRL>
+__global__ __launch_bounds__(kWave) void cmd_step_kernel(SimView<R> v, const Consts<R>* __restrict__ cp,
+                                                         const void* __restrict__ actions, int mode, R max_rpm,
+                                                         R* __restrict__ obs20) {
+  __shared__ R sx[MULTI ? 2 * kWave : 1], sy[MULTI ? 2 * kWave : 1], sz[MULTI ? 2 * kWave : 1];
+  __shared__ R rows[20 * kPad];   // the block's state20 rows, column-major (rows20_copy_out)
+  const Consts<R>& c = *cp;
+  const int tid = threadIdx.x;
+  const int D = MULTI ? v.D : 1;
+  const int d = MULTI ? tid % D : 0;
+  const int base = tid - d;
+  const long long n0 = (long long)blockIdx.x * v.tpb;
+  const long long n = n0 + tid;
+  const long long nleft = v.N - n0;
+  const int nact = (int)(nleft < v.tpb ? nleft : v.tpb);   // drones owned by this block
+  const bool active = tid < nact;
+  const long long nn = active ? n : n0;   // inactive lanes: the block's first drone (step_kernel)
+  const bool drag = pf_on<PF>(c.flags, F_DRAG);
+  const DcPairs dcp = dc_enabled<MULTI, PF>(c.flags) ? dc_pairs_for(v, tid, nact) : dc_pairs_none();
+  Drone<R> s;
+  R last[4];
+  load_drone(v, nn, s, last, drag);
+  DynK<R> dk = dyn_consts(c);
+  R rpm[4];
+  R cs[9];
+  if (CTRL) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) cs[k] = v.ctrl[tidx(nn, k, 9)];
+  }
+  cmd_to_rpm<R, CTRL>(c, mode, actions, nn, max_rpm, s, cs, rpm);
+  // the same RPMs and wrench drive every substep; the drag of substep 1 sees the previous step's
+  // RPMs (BaseAviary.py:359-372)
+  R W[4];
+  rpm_wrench<R, PF>(rpm, dk, c, W);
+  if (PF == 0) {   // the write-only world ang_v from the last substep only
+    for (int it = 0; it < dk.nsub - 1; ++it)
+      substep_block<R, MULTI, PF, false>(s, rpm, W, last, c, dk, sx, sy, sz, tid, base, D, DwPairs{0, 0}, nullptr, dcp);
+    substep_block<R, MULTI, PF, true>(s, rpm, W, last, c, dk, sx, sy, sz, tid, base, D, DwPairs{0, 0}, nullptr, dcp);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) last[k] = rpm[k];
+  } else {         // one copy of the substep (its plane and pair solves are most of the kernel's code)
+    for (int it = 0; it < dk.nsub; ++it) {
+      substep_block<R, MULTI, PF, true>(s, rpm, W, last, c, dk, sx, sy, sz, tid, base, D, DwPairs{0, 0}, nullptr, dcp);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) last[k] = rpm[k];   // self.last_clipped_action = clipped_action  :372
+    }
+  }
+  if (obs20) {
+    R o[20];
+    state20_row(s, last, o);
+#pragma unroll
+    for (int k = 0; k < 20; ++k) rows[k * kPad + tid] = o[k];
+    wave_lds_sync();
+    rows20_copy_out(rows, tid, nact, obs20 + n0 * 20);
+  }
+  if (!active) return;
+  store_drone(v, n, s, last);
+  unmark_last_in_ring(v, n);
+  if (CTRL) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) v.ctrl[tidx(n, k, 9)] = cs[k];
+  }
+  if (d == 0) {   // step_counter += PYB_STEPS_PER_CTRL (:382); the ring head stays
+    int* sc = &v.ctr[MULTI ? n / D : n].x;
+    *sc = *sc + dk.nsub;
+  }
+}
+
+// gpd_cmd_step for envs of 65 .. 1024 drones: one env per workgroup of ceil(D / 64) waves
+// (integrate_kernel_wide), rows stored per lane.
+template <typename R, int MAXT, bool CTRL>
+__global__ __launch_bounds__(MAXT) void cmd_step_kernel_wide(SimView<R> v, const Consts<R>* __restrict__ cp,
+                                                             const void* __restrict__ actions, int mode, R max_rpm,
+                                                             R* __restrict__ obs20) {
+  __shared__ R sx[MAXT], sy[MAXT], sz[MAXT];
+  const Consts<R>& c = *cp;
+  const int D = v.D;
+  const int d = threadIdx.x;
+  const bool active = d < D;
+  const long long n = (long long)blockIdx.x * D + (active ? d : (d & ~(kWave - 1)));   // (step_kernel_wide)
+  Drone<R> s;
+  R last[4];
+  load_drone(v, n, s, last, true);
+  DynK<R> dk = dyn_consts(c);
+  const int nw = (D + kWave - 1) / kWave;
+  R rpm[4];
+  R cs[9];
+  if (CTRL) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) cs[k] = v.ctrl[tidx(n, k, 9)];
+  }
+  cmd_to_rpm<R, CTRL>(c, mode, actions, n, max_rpm, s, cs, rpm);
+  R W[4];
+  rpm_wrench<R, kPfRuntime>(rpm, dk, c, W);
+  for (int it = 0; it < dk.nsub; ++it) {
+    const R dw = wide_downwash(s, sx, sy, sz, d, active, 0, D, c, dk.flags);
+    if (nw > 1) dyn_substep<R, kPfRuntime, true, 16>(s, rpm, W, last, dw, c, dk);
+    else dyn_substep<R, kPfRuntime, true, 1>(s, rpm, W, last, dw, c, dk);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) last[k] = rpm[k];
+  }
+  if (!active) return;
+  if (obs20) {
+    R o[20];
+    state20_row(s, last, o);
+    R* dst = obs20 + n * 20;
+#pragma unroll
+    for (int k = 0; k < 20; ++k) dst[k] = o[k];
+  }
+  store_drone(v, n, s, last);
+  unmark_last_in_ring(v, n);
+  if (CTRL) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) v.ctrl[tidx(n, k, 9)] = cs[k];
+  }
+  if (d == 0) {
+    int* sc = &v.ctr[blockIdx.x].x;
+    *sc = *sc + dk.nsub;
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// gpd_adjacency: BaseAviary._getAdjacencyMatrix (:658-675) of every env from the stored
+// positions, one thread per (env, i, j): 1 on the diagonal, else |pos_i - pos_j| < radius with
+// np.linalg.norm's rounding of each product and sum (no FP contraction).  radius = inf: all ones.
+template <typename R>
+__global__ __launch_bounds__(256) void adjacency_kernel(SimView<R> v, double radius, uint8_t* __restrict__ out) {
+#pragma clang fp contract(off)
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long D = v.D, total = (long long)v.N * D;
+  if (idx >= total) return;
+  const long long ni = idx / D;              // drone i (global)
+  const int j = (int)(idx - ni * D);
+  const long long nj = ni / D * D + j;       // drone j of the same env
+  uint8_t adj = 1;
+  if (ni != nj) {
+    const R dx = v.state[tidx(ni, 0, kStateComps)] - v.state[tidx(nj, 0, kStateComps)];
+    const R dy = v.state[tidx(ni, 1, kStateComps)] - v.state[tidx(nj, 1, kStateComps)];
+    const R dz = v.state[tidx(ni, 2, kStateComps)] - v.state[tidx(nj, 2, kStateComps)];
+    const R dist = g_sqrt((dx * dx + dy * dy) + dz * dz);
+    adj = (double)dist < radius ? 1 : 0;
+  }
+  out[idx] = adj;
+}
+
+}  // namespace gpd

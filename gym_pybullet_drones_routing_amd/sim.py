@@ -31,6 +31,9 @@ _PHYSICS = {
     Physics.PYB_DW: ("bullet", "dw"),
     Physics.PYB_GND_DRAG_DW: ("bullet", "gnd", "drag", "dw"),
 }
+# cmd_step modes: (GPD_CMD_*, action width, actions in the sim's real dtype (else float32))
+_CMD_MODES = {"rpm": (_lib.GPD_CMD_RPM, 4, True), "vel": (_lib.GPD_CMD_VEL, 4, False),
+              "waypoint": (_lib.GPD_CMD_WAYPOINT, 7, True)}
 _warned = set()
 
 
@@ -206,6 +209,7 @@ class BatchedAviarySim:
         self._step_fn = self._lib.gpd_step
         self._out_ptrs = (_ptr(self.obs), _ptr(self.reward), _ptr(self.terminated), _ptr(self.truncated))
         self._tobs_ptr = _ptr(self.terminal_obs)
+        self._obs20 = None              # cmd_step's [E, D, 20] rows, allocated on first use (not in out_pack)
         self.reset()
 
     def _field(self, name, dtype, shape):
@@ -293,6 +297,67 @@ class BatchedAviarySim:
             for a in seq:
                 self.step(a, terminal_obs=terminal_obs)
         return g
+
+    # ------------------------------------------------------------------ command step (CtrlAviary / VelocityAviary)
+    def cmd_step(self, actions, mode="rpm"):
+        """One ``env.step()`` of the reference's CtrlAviary / VelocityAviary for every env, in one
+        launch (``gpd_cmd_step``).  ``mode``:
+
+        * ``"rpm"``: ``actions`` [E, D, 4] in the sim's real dtype, clipped to [0, MAX_RPM]
+          (CtrlAviary.py:140);
+        * ``"vel"``: ``actions`` [E, D, 4] float32 velocity commands through DSLPIDControl
+          (VelocityAviary.py:148-168);
+        * ``"waypoint"``: ``actions`` [E, D, 7] real = target_pos(3), target yaw, target_vel(3):
+          ``DSLPIDControl.computeControl`` on the device (the loop of the reference's examples/pid.py).
+
+        ``"vel"`` and ``"waypoint"`` need a sim created with a PID action type.  Returns the
+        sim-owned [E, D, 20] state vectors (real dtype), overwritten by the next call.  No
+        reward / done flags / auto-reset; the RL step's action history is left alone."""
+        try:
+            code, width, real = _CMD_MODES[mode]
+        except KeyError:
+            raise ValueError(f"mode must be one of {sorted(_CMD_MODES)}, got {mode!r}") from None
+        dtype = self.real_dtype if real else torch.float32
+        a = actions
+        if not (isinstance(a, torch.Tensor) and a.device == self.device and a.dtype == dtype and a.is_contiguous()):
+            a = torch.as_tensor(a, dtype=dtype, device=self.device).contiguous()
+        if a.numel() != self.n_drones * width:
+            raise ValueError(f"actions must have {self.n_envs}x{self.drones_per_env}x{width} elements")
+        with torch.cuda.device(self.device):
+            self._call("gpd_cmd_step", code, _ptr(a), _ptr(self._cmd_rows()), _stream(self.device))
+        return self._obs20
+
+    def _cmd_rows(self):
+        if self._obs20 is None:
+            self._obs20 = torch.zeros((self.n_envs, self.drones_per_env, 20), dtype=self.real_dtype,
+                                      device=self.device)
+        return self._obs20
+
+    def capture_cmd_graph(self, actions_seq, mode="rpm"):
+        """:meth:`capture_graph` for :meth:`cmd_step`: ``len(actions_seq)`` consecutive command
+        steps in one HIP graph.  gpd_cmd_step keeps no host state (the step counters live in
+        device memory), so a recorded sequence stays valid for any number of replays; the action
+        tensors must already be what ``cmd_step`` passes on (device, dtype, contiguous)."""
+        _, width, real = _CMD_MODES[mode]
+        dtype = self.real_dtype if real else torch.float32
+        for a in actions_seq:
+            if not (isinstance(a, torch.Tensor) and a.device == self.device and a.dtype == dtype
+                    and a.is_contiguous() and a.numel() == self.n_drones * width):
+                raise ValueError(f"capture_cmd_graph needs contiguous {dtype} action tensors on the sim's device")
+        self._cmd_rows()    # allocated outside the capture
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.device(self.device), torch.cuda.graph(g):
+            for a in actions_seq:
+                self.cmd_step(a, mode)
+        return g
+
+    def adjacency(self, radius=np.inf):
+        """BaseAviary._getAdjacencyMatrix (:658-675) of every env: [E, D, D] uint8 on the device."""
+        out = torch.empty((self.n_envs, self.drones_per_env, self.drones_per_env), dtype=torch.uint8,
+                          device=self.device)
+        with torch.cuda.device(self.device):
+            self._call("gpd_adjacency", float(radius), _ptr(out), _stream(self.device))
+        return out
 
     # ------------------------------------------------------------------ raw physics
     def integrate(self, rpm, record=False):

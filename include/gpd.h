@@ -76,7 +76,7 @@ extern "C" {
 #define GPD_ACT_ONE_D_PID 4   /* width 1: DSLPIDControl to pos + (0,0,0.1a)         :226-235 */
 
 /* Task hooks (reward / terminated / truncated) */
-#define GPD_TASK_NONE 0       /* raw aviary: reward -1, never done (CtrlAviary-like) */
+#define GPD_TASK_NONE 0       /* raw aviary: reward -1, never done (CtrlAviary / VelocityAviary) */
 #define GPD_TASK_HOVER 1      /* HoverAviary.py:68-117 */
 #define GPD_TASK_MULTIHOVER 2 /* MultiHoverAviary.py:75-130 */
 
@@ -203,6 +203,30 @@ int gpd_step_seq(gpd_sim* sim, const float* actions, int n_slots, int n_steps, f
  * every drone; each substep is followed by the readback (PYB_STEPS_PER_CTRL = 1 cadence).
  * traj (nullable) receives the 20-float state after every substep, [n_sub][N][20] real. */
 int gpd_integrate(gpd_sim* sim, const void* rpm, int n_sub, void* traj, void* stream);
+
+/* The command step: one env.step() of the reference's CtrlAviary / VelocityAviary for every env
+ * in one launch - command -> RPMs once, PYB_STEPS_PER_CTRL substeps on them (BaseAviary.py:343-372),
+ * the final readback, step_counter += PYB_STEPS_PER_CTRL.  No reward, no done flags, no
+ * auto-reset; the action history of the RL step is neither read nor written.
+ *   GPD_CMD_RPM       actions [N][4] real: np.clip(a, 0, MAX_RPM)   (envs/CtrlAviary.py:140)
+ *   GPD_CMD_VEL       actions [N][4] float: DSLPIDControl to the velocity SPEED_LIMIT*|a3|*a/|a|,
+ *                     holding the position and yaw of the last readback (envs/VelocityAviary.py:148-168)
+ *   GPD_CMD_WAYPOINT  actions [N][7] real = target_pos(3) target_yaw target_vel(3):
+ *                     DSLPIDControl.computeControl(target_pos, target_rpy=(0, 0, yaw), target_vel)
+ *                     (control/DSLPIDControl.py:82-145; the loop body of examples/pid.py)
+ * VEL and WAYPOINT need a sim created with a PID action type (its controller state, see
+ * gpd_get_ctrl_state), else GPD_EINVAL.  obs20 (nullable) receives the 20-float state vectors
+ * [N][20] real (_computeObs, envs/CtrlAviary.py:106-117).  RPM / VEL actions and obs20 must be
+ * 16-byte aligned.  Works on any sim, interleaved with the other calls; a fixed-argument launch
+ * (graph-capturable). */
+#define GPD_CMD_RPM 0
+#define GPD_CMD_VEL 1
+#define GPD_CMD_WAYPOINT 2
+int gpd_cmd_step(gpd_sim* sim, int mode, const void* actions, void* obs20, void* stream);
+
+/* BaseAviary._getAdjacencyMatrix (:658-675) of every env: out [E][D][D] uint8 (device memory),
+ * 1 on the diagonal and where |pos_i - pos_j| < radius (radius = inf: all ones). */
+int gpd_adjacency(gpd_sim* sim, double radius, uint8_t* out, void* stream);
 
 /* 20-float state vectors [N][20] real (BaseAviary.py:541-561). */
 int gpd_get_state20(gpd_sim* sim, void* out, void* stream);
