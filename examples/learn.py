@@ -174,9 +174,10 @@ class GraphedMinibatch:
                 opt.zero_grad(set_to_none=True)
                 self._body()
         torch.cuda.current_stream(device).wait_stream(s)
+        from gym_pybullet_drones_routing_amd.sim import graph_capture
         self.graph = torch.cuda.CUDAGraph()
         opt.zero_grad(set_to_none=True)
-        with torch.cuda.graph(self.graph):
+        with graph_capture(self.graph, device):
             self._body()
         with torch.no_grad():                        # undo the warm-up steps, in place
             for p, p0 in zip(policy.parameters(), params0):
@@ -271,8 +272,9 @@ class FusedRollout:
             self.env.rollout(self.T, self._seq)      # the ROLLOUT command: every rank replays its graph
             return
         if self.graph is None:
+            from gym_pybullet_drones_routing_amd.sim import graph_capture
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
+            with graph_capture(self.graph, torch.cuda.current_device()):
                 self._seq()
         self.graph.replay()
 

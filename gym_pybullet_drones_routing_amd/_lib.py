@@ -36,7 +36,12 @@ EXPORTED = ("gpd_abi_version", "gpd_last_error", "gpd_default_params", "gpd_crea
             "gpd_get_raw_state", "gpd_set_raw_state", "gpd_get_step_counters",
             "gpd_set_step_counters", "gpd_state_bytes", "gpd_save_state", "gpd_load_state",
             "gpd_default_pid_params", "gpd_set_pid_params", "gpd_get_ctrl_state", "gpd_set_ctrl_state",
-            "gpd_nonfinite", "gpd_cmd_step", "gpd_adjacency", "gpd_pack_layout_of", "gpd_handoff_pack", "gpd_handoff_unpack")
+            "gpd_nonfinite", "gpd_cmd_step", "gpd_adjacency", "gpd_pack_layout_of", "gpd_handoff_pack", "gpd_handoff_unpack",
+            "gpd_create_het", "gpd_set_env_params", "gpd_set_env_init", "gpd_env_derive")
+
+# gpd_env_params: the per-env part of the drone parameters, in the struct's field order
+ENV_PARAM_NAMES = ("m", "arm", "thrust2weight", "ixx", "iyy", "izz", "kf", "km",
+                   "gnd_eff_coeff", "drag_coeff_xy", "drag_coeff_z")
 
 
 class GpdLibraryError(RuntimeError):
@@ -55,6 +60,11 @@ class DroneParams(ctypes.Structure):
         "collision_h", "collision_r", "collision_z_offset", "max_speed_kmh",
         "gnd_eff_coeff", "prop_radius", "drag_coeff_xy", "drag_coeff_z",
         "dw_coeff_1", "dw_coeff_2", "dw_coeff_3")] + [("prop_pos", (ctypes.c_double * 3) * 4)]
+
+
+class EnvParams(ctypes.Structure):
+    """gpd_env_params: one env's randomisable drone parameters (11 doubles)."""
+    _fields_ = [(n, ctypes.c_double) for n in ENV_PARAM_NAMES]
 
 
 class PidParams(ctypes.Structure):
@@ -135,6 +145,10 @@ def load():
         "gpd_pack_layout_of": (ci, [i, i, i, ctypes.POINTER(PackLayout)]),
         "gpd_handoff_pack": (ci, [vp, ctypes.POINTER(PackLayout), vp]),
         "gpd_handoff_unpack": (ci, [vp, i, ctypes.c_longlong, ctypes.POINTER(PackLayout), vp, vp, vp, vp, vp, vp]),
+        "gpd_create_het": (ci, [ctypes.POINTER(DroneParams), ctypes.POINTER(Config), vp, vp, vp, ctypes.POINTER(vp)]),
+        "gpd_set_env_params": (ci, [vp, vp]),
+        "gpd_set_env_init": (ci, [vp, vp, vp]),
+        "gpd_env_derive": (ci, [ctypes.POINTER(DroneParams), vp, i, ctypes.POINTER(Constants)]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(lib, name) and os.environ.get("GPD_ALLOW_ABI_MISMATCH"):

@@ -60,6 +60,20 @@ def parse_urdf(path, drone_model=DroneModel.CF2X):
     return p
 
 
+def randomized_params(n_envs, frac=0.1, seed=0, drone_model=DroneModel.CF2X):
+    """Per-env domain randomisation for ``BatchedAviarySim(env_params=...)``: every one of the 11
+    per-env parameters (``_lib.ENV_PARAM_NAMES``, drawn in that order) uniform in
+    ``[1 - frac, 1 + frac]`` times the model's nominal value, from ``numpy.random.default_rng(seed)``.
+    Returns {name: float64 array [n_envs]}."""
+    import numpy as np
+    if not 0.0 <= frac < 1.0:
+        raise ValueError("frac must be in [0, 1): every parameter has to stay positive")
+    nominal = default_params(drone_model)
+    rng = np.random.default_rng(seed)
+    return {name: getattr(nominal, name) * rng.uniform(1.0 - frac, 1.0 + frac, int(n_envs))
+            for name in _lib.ENV_PARAM_NAMES}
+
+
 def params_dict(p):
     """ctypes DroneParams -> plain dict (for printing / tests)."""
     d = {name: getattr(p, name) for name, _ in p._fields_ if name != "prop_pos"}

@@ -135,8 +135,14 @@ struct gpd_sim {
   void* d_dc_rows = nullptr;
   long long dc_row_stride = 0;
   double bound_xy;
-  std::vector<double> init_tmpl;  // [D][10]
-  std::vector<double> target;     // [D][3]
+  std::vector<double> init_tmpl;  // [D][10]; het: [E][D][10]
+  std::vector<double> target;     // [D][3]; het: [E][D][3]
+  // heterogeneous sim (gpd_create_het; kernels in gpd_step_het.h)
+  bool het = false;
+  void* d_etab = nullptr;         // [kHetCols][epad] per-env constants in the sim's real type
+  long long epad = 0;             // E rounded up to 64
+  std::vector<gpd_env_params> env_rows;   // [E]
+  std::vector<double> het_xyz, het_rpy;   // [E][D][3]
 };
 
 namespace {
@@ -291,8 +297,28 @@ const void* step_fn_pid(bool multi, int flags) {
     default: return (const void*)step_kernel<R, ACT, false, kPfRuntime>;
   }
 }
+// het sims (gpd_step_het.h): the flag sets compiled in as step_fn_act chooses them (plain DYN,
+// ground effect + drag, downwash in multi-drone envs), the other DYN combinations at run time
+template <typename R, int ACT>
+const void* step_het_fn_act(bool multi, int flags) {
+  if (multi) {
+    switch (flags) {
+      case 0: return (const void*)step_kernel_het<R, ACT, true, 0>;
+      case F_DW: return (const void*)step_kernel_het<R, ACT, true, F_DW>;
+      default: return (const void*)step_kernel_het<R, ACT, true, kPfRuntime>;
+    }
+  }
+  switch (flags) {
+    case 0: return (const void*)step_kernel_het<R, ACT, false, 0>;
+    case kPfAero: return (const void*)step_kernel_het<R, ACT, false, kPfAero>;
+    default: return (const void*)step_kernel_het<R, ACT, false, kPfRuntime>;
+  }
+}
 template <typename R>
 const void* step_kernel_fn(const gpd_sim* s) {
+  if (s->het)
+    return s->cfg.act_type == GPD_ACT_RPM ? step_het_fn_act<R, ACT_RPM>(s->D > 1, s->cfg.physics_flags)
+                                          : step_het_fn_act<R, ACT_ONE_D_RPM>(s->D > 1, s->cfg.physics_flags);
   if (s->step_waves == 3)
     return s->cfg.act_type == GPD_ACT_RPM ? (const void*)step_kernel_duo<R, ACT_RPM, true>
                                           : (const void*)step_kernel_duo<R, ACT_ONE_D_RPM, true>;
@@ -353,6 +379,10 @@ int upload_tables(gpd_sim* s) {
     f = step_kernel_fn<R>(s);
     HIP_TRY(hipFuncGetAttributes(&fa, f));
   }
+  if (fa.sharedSizeBytes + (size_t)s->tile_bytes > kLdsBytes && s->het)   // (gpd_create_het's host-side bound is the
+    // first line of defence; this is the kernel's own figure)
+    return fail(GPD_EUNSUPPORTED, "gpd_create_het: the action history does not fit the one-wave step kernel's "
+                                  "observation tile beside its static LDS");
   if (fa.sharedSizeBytes + (size_t)s->tile_bytes > kLdsBytes)
     return fail(GPD_EUNSUPPORTED, "gpd_create: ctrl_freq too high for drone <-> drone contact (observation tile + "
                                   "the step kernel's LDS exceed 160 KiB; GPD_F_NO_DRONE_CONTACT lifts the limit)");
@@ -388,7 +418,11 @@ int settle_last(gpd_sim* s, hipStream_t st) {
   if (!(s->wt & 4)) return GPD_OK;
   const SimView<R> v = make_view<R>(s);
   const Consts<R>* c = (const Consts<R>*)s->d_consts;
-  hipLaunchKernelGGL((last_from_ring_kernel<R>), dim3(grid_for(s->N, 256)), dim3(256), 0, st, v, c);
+  if (s->het)   // the env's own float32 hover constant
+    hipLaunchKernelGGL((last_from_ring_kernel_het<R>), dim3(grid_for(s->N, 256)), dim3(256), 0, st, v,
+                       (const R*)s->d_etab, s->epad);
+  else
+    hipLaunchKernelGGL((last_from_ring_kernel<R>), dim3(grid_for(s->N, 256)), dim3(256), 0, st, v, c);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemsetAsync(s->d_ctr + s->E, 0, sizeof(int2), st));
   return GPD_OK;
@@ -418,6 +452,15 @@ int launch_step(gpd_sim* s, const float* actions, float* obs, float* reward, uin
   }
   const unsigned grid = grid_for(s->N, s->tpb);
   const size_t lds = (size_t)s->tile_bytes;
+  if (s->het) {
+    typedef void (*HetFn)(R*, const float*, int2*, const Consts<R>*, const R*, int, int, long long, SimView<R>,
+                          StepIO<R>);
+    const HetFn fh = (HetFn)step_kernel_fn<R>(s);
+    hipLaunchKernelGGL(fh, dim3(grid), dim3(kWave), lds, st, v.state, io.actions, v.ctr, c, (const R*)s->d_etab, v.N,
+                       v.tpb, s->epad, v, io);
+    HIP_TRY(hipGetLastError());
+    return GPD_OK;
+  }
   typedef void (*StepFn)(R*, const float*, int2*, const Consts<R>*, long long, int, int, SimView<R>, StepIO<R>);
   const StepFn f = (StepFn)step_kernel_fn<R>(s);
   hipLaunchKernelGGL(f, dim3(grid), dim3(s->step_waves * kWave), lds, st, v.state, io.actions, v.ctr, c, v.npad,
@@ -442,6 +485,21 @@ int launch_integrate(gpd_sim* s, const void* rpm, int n_sub, void* traj, hipStre
                      : (s->D <= 512 ? integrate_wide_fn<R, 512>(tr != nullptr) : integrate_wide_fn<R, 1024>(tr != nullptr));
     void* args[] = {(void*)&v, (void*)&c, (void*)&r, (void*)&n_sub, (void*)&tr};
     HIP_TRY(hipLaunchKernel(fw, dim3(s->E), dim3((s->D + kWave - 1) / kWave * kWave), args, 0, st));
+    return GPD_OK;
+  }
+  if (s->het) {
+    const bool multi = s->D > 1;
+    const void* fh;
+    if (tr) fh = multi ? (const void*)integrate_kernel_het<R, true, kPfRuntime, true>
+                       : (const void*)integrate_kernel_het<R, false, kPfRuntime, true>;
+    else if (multi) fh = plain ? (const void*)integrate_kernel_het<R, true, 0, false>
+                               : (const void*)integrate_kernel_het<R, true, kPfRuntime, false>;
+    else fh = plain ? (const void*)integrate_kernel_het<R, false, 0, false>
+                    : (const void*)integrate_kernel_het<R, false, kPfRuntime, false>;
+    const R* etab = (const R*)s->d_etab;
+    long long epad = s->epad;
+    void* hargs[] = {(void*)&v, (void*)&c, (void*)&etab, (void*)&epad, (void*)&r, (void*)&n_sub, (void*)&tr};
+    HIP_TRY(hipLaunchKernel(fh, dim3(grid), dim3(kWave), hargs, 0, st));
     return GPD_OK;
   }
   const void* f;
@@ -513,7 +571,10 @@ int launch_adjacency(gpd_sim* s, double radius, uint8_t* out, hipStream_t st) {
 template <typename R>
 int launch_reset(gpd_sim* s, const uint8_t* mask, float* obs, hipStream_t st) {
   const SimView<R> v = make_view<R>(s);
-  hipLaunchKernelGGL((reset_kernel<R>), dim3(grid_for(s->N, 256)), dim3(256), 0, st, v, mask, obs);
+  if (s->het)   // every drone's own template
+    hipLaunchKernelGGL((reset_kernel_het<R>), dim3(grid_for(s->N, 256)), dim3(256), 0, st, v, mask, obs);
+  else
+    hipLaunchKernelGGL((reset_kernel<R>), dim3(grid_for(s->N, 256)), dim3(256), 0, st, v, mask, obs);
   HIP_TRY(hipGetLastError());
   return GPD_OK;
 }
@@ -555,10 +616,128 @@ void free_sim(gpd_sim* s) {
   if (s->d_init) (void)hipFree(s->d_init);
   if (s->d_target) (void)hipFree(s->d_target);
   if (s->d_consts) (void)hipFree(s->d_consts);
+  if (s->d_etab) (void)hipFree(s->d_etab);
   if (s->d_dc_tab) (void)hipFree(s->d_dc_tab);
   if (s->d_dc_rows) (void)hipFree(s->d_dc_rows);
   delete s;
 }
+
+// ---- heterogeneous sims (gpd_create_het)
+// static LDS of step_kernel_het beside the observation tile: 0 for single-drone envs, 7.5 KiB for
+// f64 multi-drone ones (positions, reward / distance / flag reduction, the downwash pair buffer)
+constexpr size_t kHetStaticLds = 8192;
+
+struct HetArgs {
+  const gpd_env_params* rows;   // [E] or null
+  const double* xyzs;           // [E][D][3] or null
+  const double* rpys;           // [E][D][3] or null
+};
+
+// the reset template of one drone: INIT_XYZS and the orientation the client stores
+// (BaseAviary.py:194-207, :486-491, :509-519)
+void pose_template(const double xyz[3], const double rpy[3], double t[10]) {
+  double q0[4], qraw[4], qn[4], e[3];
+  h_quat_from_euler(rpy, q0);
+  h_roundtrip(q0, qraw);  // loadURDF stores the orientation through a btTransform
+  h_roundtrip(qraw, qn);  // readback (:517)
+  h_euler(qn, e);         // :518
+  t[0] = xyz[0]; t[1] = xyz[1]; t[2] = xyz[2];
+  t[3] = qraw[0]; t[4] = qraw[1]; t[5] = qraw[2]; t[6] = qraw[3];
+  t[7] = e[0]; t[8] = e[1]; t[9] = e[2];
+}
+
+gpd_env_params env_row_of(const gpd_drone_params& P) {
+  return gpd_env_params{P.m, P.arm, P.thrust2weight, P.ixx, P.iyy, P.izz, P.kf, P.km,
+                        P.gnd_eff_coeff, P.drag_coeff_xy, P.drag_coeff_z};
+}
+
+// self.MAX_RPM**2 as Python evaluates it: libm's pow(x, 2.0), which is not correctly rounded in
+// every libm and then differs from x*x in the last bit (seen on one row in a thousand); the
+// exponent is opaque so that the compiler cannot turn the call into a multiply
+double py_square(double x) {
+  volatile double two = 2.0;
+  return std::pow(x, two);
+}
+
+// BaseAviary.py:117-128 for one env row, operation for operation (no FP contraction)
+void derive_row(const gpd_drone_params& base, const gpd_env_params& r, gpd_constants& K) {
+#pragma clang fp contract(off)
+  std::memset(&K, 0, sizeof(K));
+  K.gravity = 9.8 * r.m;
+  K.hover_rpm = std::sqrt(K.gravity / (4 * r.kf));
+  K.max_rpm = std::sqrt((r.thrust2weight * K.gravity) / (4 * r.kf));
+  const double mr2 = py_square(K.max_rpm);
+  K.max_thrust = 4 * r.kf * mr2;
+  K.max_xy_torque = base.model == GPD_MODEL_CF2P ? r.arm * r.kf * mr2 : (2 * r.arm * r.kf * mr2) / std::sqrt(2.0);
+  K.max_z_torque = 2 * r.km * mr2;
+  K.gnd_eff_h_clip = 0.25 * base.prop_radius * std::sqrt((15 * mr2 * r.kf * r.gnd_eff_coeff) / K.max_thrust);
+}
+
+int check_env_rows(const char* fn, const gpd_env_params* rows, int n) {
+  static const char* const names[11] = {"m", "arm", "thrust2weight", "ixx", "iyy", "izz", "kf", "km",
+                                        "gnd_eff_coeff", "drag_coeff_xy", "drag_coeff_z"};
+  for (int e = 0; e < n; ++e) {
+    const double* f = &rows[e].m;
+    for (int k = 0; k < 11; ++k) {
+      const bool aero = k >= 8;   // the three aero coefficients may be 0
+      if (!std::isfinite(f[k]) || f[k] < 0.0 || (!aero && f[k] == 0.0))
+        return fail(GPD_EINVAL, std::string(fn) + ": env_params field " + names[k] + " of env " + std::to_string(e) +
+                                    " must be finite and " + (aero ? ">= 0" : "> 0"));
+    }
+  }
+  return GPD_OK;
+}
+static_assert(sizeof(gpd_env_params) == 11 * sizeof(double), "gpd_env_params is 11 packed doubles");
+
+int check_poses(const char* fn, const char* what, const double* p, long long n_drones, int D) {
+  if (!p) return GPD_OK;
+  for (long long i = 0; i < n_drones * 3; ++i)
+    if (!std::isfinite(p[i]))
+      return fail(GPD_EINVAL, std::string(fn) + ": " + what + " of env " + std::to_string(i / (3LL * D)) +
+                                  " drone " + std::to_string((i / 3) % D) + " is not finite");
+  return GPD_OK;
+}
+
+// [E][D][10] templates and [E][D][3] targets from the stored het poses
+void het_templates(gpd_sim* s) {
+  const int task = s->cfg.task;
+  for (int e = 0; e < s->E; ++e)
+    for (int d = 0; d < s->D; ++d) {
+      const size_t n = (size_t)e * s->D + d;
+      const double* xyz = &s->het_xyz[n * 3];
+      pose_template(xyz, &s->het_rpy[n * 3], &s->init_tmpl[n * 10]);
+      double* tg = &s->target[n * 3];
+      tg[0] = tg[1] = tg[2] = 0.0;
+      if (task == GPD_TASK_HOVER) {           // HoverAviary.py:51
+        tg[2] = 1.0;
+      } else if (task == GPD_TASK_MULTIHOVER) {  // MultiHoverAviary.py:71
+        tg[0] = xyz[0]; tg[1] = xyz[1]; tg[2] = xyz[2] + 1.0 / (d + 1);
+      }
+    }
+}
+
+// the per-env constant table: derived in double with make_consts' expressions, rounded once to R
+template <typename R>
+int upload_env_table(gpd_sim* s) {
+  std::vector<R> tab((size_t)kHetCols * s->epad, R(0));
+  for (int e = 0; e < s->E; ++e) {
+    const gpd_env_params& r = s->env_rows[e];
+    gpd_constants K;
+    derive_row(s->P, r, K);
+    auto put = [&](int col, double v) { tab[(size_t)col * s->epad + e] = (R)v; };
+    put(kHetM, r.m); put(kHetGravity, K.gravity); put(kHetInvM, 1.0 / r.m);
+    put(kHetKf, r.kf); put(kHetKm, r.km); put(kHetL, r.arm); put(kHetLs2, r.arm / std::sqrt(2.0));
+    put(kHetJx, r.ixx); put(kHetJy, r.iyy); put(kHetJz, r.izz);
+    put(kHetIjx, 1.0 / r.ixx); put(kHetIjy, 1.0 / r.iyy); put(kHetIjz, 1.0 / r.izz);
+    put(kHetHover, (double)(float)K.hover_rpm);   // float32(HOVER_RPM), exact in either real type
+    put(kHetGeCoeff, r.gnd_eff_coeff); put(kHetGeClip, K.gnd_eff_h_clip);
+    put(kHetDragXy, r.drag_coeff_xy); put(kHetDragZ, r.drag_coeff_z);
+  }
+  HIP_TRY(hipMemcpy(s->d_etab, tab.data(), tab.size() * sizeof(R), hipMemcpyHostToDevice));
+  return GPD_OK;
+}
+
+int create_impl(const gpd_drone_params* params, const gpd_config* cfg, const HetArgs* het, gpd_sim** out);
 
 }  // namespace
 
@@ -604,6 +783,82 @@ int gpd_default_params(int model, gpd_drone_params* out) {
 }
 
 int gpd_create(const gpd_drone_params* params, const gpd_config* cfg, gpd_sim** out) {
+  return create_impl(params, cfg, nullptr, out);
+}
+
+int gpd_create_het(const gpd_drone_params* params, const gpd_config* cfg, const gpd_env_params* env_params_host,
+                   const double* init_xyzs_host, const double* init_rpys_host, gpd_sim** out) {
+  if (!params || !cfg || !out) return fail(GPD_EINVAL, "gpd_create_het: NULL argument");
+  *out = nullptr;
+  const gpd_config& C = *cfg;
+  // what a het sim supports, then every row and pose: all before the first device call
+  if (C.n_envs < 1) return fail(GPD_EINVAL, "gpd_create_het: n_envs must be >= 1");
+  if (C.drones_per_env < 1) return fail(GPD_EINVAL, "gpd_create_het: drones_per_env must be >= 1");
+  if (C.physics_flags & GPD_F_BULLET)
+    return fail(GPD_EUNSUPPORTED, "gpd_create_het: GPD_F_BULLET (Physics.PYB*) is not supported with per-env "
+                                  "parameters: the contact solves hold mass and inertia in derived rows; use the DYN "
+                                  "integrator (Physics.DYN)");
+  if (C.physics_flags & ~kHetFlags) return fail(GPD_EINVAL, "gpd_create_het: unknown or contact-only physics flag");
+  if (C.act_type != GPD_ACT_RPM && C.act_type != GPD_ACT_ONE_D_RPM)
+    return fail(GPD_EUNSUPPORTED, "gpd_create_het: the PID action types are not supported with per-env parameters "
+                                  "(DSLPIDControl is tuned for the nominal drone); use GPD_ACT_RPM or GPD_ACT_ONE_D_RPM");
+  if (C.drones_per_env > kWave)
+    return fail(GPD_EUNSUPPORTED, "gpd_create_het: drones_per_env > 64 needs the multi-wave step kernel, which has no "
+                                  "per-env parameters");
+  if (C.ctrl_freq >= 2 &&
+      (size_t)step_tile_bytes(act_width(C.act_type), C.ctrl_freq / 2) + kHetStaticLds > kLdsBytes)
+    return fail(GPD_EUNSUPPORTED, "gpd_create_het: the action history (ctrl_freq // 2 slots) does not fit the one-wave "
+                                  "step kernel's observation tile; the multi-wave kernel has no per-env parameters");
+  const long long N = (long long)C.n_envs * C.drones_per_env;
+  int rc = env_params_host ? check_env_rows("gpd_create_het", env_params_host, C.n_envs) : GPD_OK;
+  if (rc == GPD_OK) rc = check_poses("gpd_create_het", "init_xyzs", init_xyzs_host, N, C.drones_per_env);
+  if (rc == GPD_OK) rc = check_poses("gpd_create_het", "init_rpys", init_rpys_host, N, C.drones_per_env);
+  if (rc != GPD_OK) return rc;
+  const HetArgs het{env_params_host, init_xyzs_host, init_rpys_host};
+  rc = create_impl(params, cfg, &het, out);
+  // the shared checks' messages under this entry point's name
+  if (rc != GPD_OK && g_err.compare(0, 11, "gpd_create:") == 0) g_err.replace(0, 10, "gpd_create_het");
+  return rc;
+}
+
+int gpd_set_env_params(gpd_sim* sim, const gpd_env_params* rows_host) {
+  if (!sim || !rows_host) return fail(GPD_EINVAL, "gpd_set_env_params: NULL argument");
+  if (!sim->het) return fail(GPD_EINVAL, "gpd_set_env_params: not a het sim (create it with gpd_create_het)");
+  int rc = check_env_rows("gpd_set_env_params", rows_host, sim->E);
+  if (rc != GPD_OK) return rc;
+  // a last action still in the ring (store-policy bit 2) is rebuilt from the env's hover column:
+  // settle it with the rows the steps ran on, before they are replaced
+  rc = settle_last_any(sim, 0);
+  if (rc != GPD_OK) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  sim->env_rows.assign(rows_host, rows_host + sim->E);
+  return sim->prec == GPD_F64 ? upload_env_table<double>(sim) : upload_env_table<float>(sim);
+}
+
+int gpd_set_env_init(gpd_sim* sim, const double* xyzs_host, const double* rpys_host) {
+  if (!sim) return fail(GPD_EINVAL, "gpd_set_env_init: NULL sim");
+  if (!sim->het) return fail(GPD_EINVAL, "gpd_set_env_init: not a het sim (create it with gpd_create_het)");
+  int rc = check_poses("gpd_set_env_init", "init_xyzs", xyzs_host, sim->N, sim->D);
+  if (rc == GPD_OK) rc = check_poses("gpd_set_env_init", "init_rpys", rpys_host, sim->N, sim->D);
+  if (rc != GPD_OK) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if (xyzs_host) sim->het_xyz.assign(xyzs_host, xyzs_host + (size_t)sim->N * 3);
+  if (rpys_host) sim->het_rpy.assign(rpys_host, rpys_host + (size_t)sim->N * 3);
+  het_templates(sim);
+  return sim->prec == GPD_F64 ? upload_tables<double>(sim) : upload_tables<float>(sim);
+}
+
+int gpd_env_derive(const gpd_drone_params* base, const gpd_env_params* rows, int n, gpd_constants* out) {
+  if (!base || !rows || !out || n < 0) return fail(GPD_EINVAL, "gpd_env_derive: NULL argument or n < 0");
+  for (int i = 0; i < n; ++i) derive_row(*base, rows[i], out[i]);
+  return GPD_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+int create_impl(const gpd_drone_params* params, const gpd_config* cfg, const HetArgs* het, gpd_sim** out) {
   if (!params || !cfg || !out) return fail(GPD_EINVAL, "gpd_create: NULL argument");
   *out = nullptr;
   const gpd_config& C = *cfg;
@@ -653,6 +908,7 @@ int gpd_create(const gpd_drone_params* params, const gpd_config* cfg, gpd_sim** 
   s->W = 12 + s->ring_len * s->A;
   s->nsub = C.pyb_freq / C.ctrl_freq;
   s->prec = C.precision;
+  s->het = het != nullptr;
   // Drones per 64-lane block.  A wave's time is set by its serial instruction stream, not by
   // how many of its lanes are active, while a CU streams the observation rows of its blocks at
   // a limited store-issue rate; so when there are too few drones to give every CU a full wave,
@@ -677,10 +933,11 @@ int gpd_create(const gpd_drone_params* params, const gpd_config* cfg, gpd_sim** 
     // the wide kernel copies the history columns without a tile (with the drone <-> drone contact
     // in its one-wave instantiation, D <= 64)
     const size_t tile = (size_t)step_tile_bytes(s->A, s->ring_len);
-    const size_t lds_rt = s->D > kWave ? 0
+    const size_t lds_rt = s->D > kWave || s->het ? 0   // (a het sim never launches that kernel)
                           : (C.precision == GPD_F64 ? runtime_step_lds<double>(C.act_type, s->D > 1)
                                                     : runtime_step_lds<float>(C.act_type, s->D > 1));
     s->wide = s->D > kWave || tile + lds_rt > (size_t)kLdsBytes;
+    if (s->het) s->wide = false;   // gpd_create_het checked D and the tile against step_kernel_het's LDS
     // envs of up to 32 drones share the wave, up to 64 / D of them, as many as leave ~2048
     // workgroups (the history copy's loads in flight: 4096 single-drone envs at ctrl_freq 480
     // 37.8 us per step with one env per workgroup, 86.7 with 64; 65536 envs 591 / 213 us);
@@ -738,7 +995,7 @@ int gpd_create(const gpd_drone_params* params, const gpd_config* cfg, gpd_sim** 
     // 5.33, but 8192 envs 5.72 -> 5.90 and 16384 envs 6.23 -> 7.20: with fuller blocks the
     // two-wave copy-out overlaps other blocks' work anyway.
     // gpd_config::step_waves overrides (1, 2 or 3).
-    const bool duo_ok = !s->wide && s->D == 1 && C.physics_flags == 0 &&
+    const bool duo_ok = !s->het && !s->wide && s->D == 1 && C.physics_flags == 0 &&
                         (C.act_type == GPD_ACT_RPM || C.act_type == GPD_ACT_ONE_D_RPM);
     int waves = !duo_ok || s->N > 65536 ? 1 : (s->N <= 4096 ? 3 : 2);
     if (C.step_waves > 0) waves = duo_ok ? std::min(3, C.step_waves) : 1;
@@ -750,7 +1007,7 @@ int gpd_create(const gpd_drone_params* params, const gpd_config* cfg, gpd_sim** 
     // (~820 B per drone: state, ring, rows) is well past the 256 MB Infinity Cache (>= 512K drones;
     // 262144 envs = 215 MB stay with the default policies, 1M envs 194 -> 145 us with STREAM,
     // 4096 envs 4.93 -> 6.31 us had it been used there)
-    s->stream = !s->duo && !s->wide && s->D == 1 && C.physics_flags == 0 &&
+    s->stream = !s->het && !s->duo && !s->wide && s->D == 1 && C.physics_flags == 0 &&
                 (C.act_type == GPD_ACT_RPM || C.act_type == GPD_ACT_ONE_D_RPM) && s->N >= (1 << 19);
     // the multi-wave kernels store their state plainly (measured 4096 envs 5.47 -> 5.37 us/step);
     // the single-wave kernel keeps write-through state stores (262144 envs 36.7 -> 35.9 us)
@@ -803,8 +1060,16 @@ int gpd_create(const gpd_drone_params* params, const gpd_config* cfg, gpd_sim** 
   }
 
   // reset template: INIT_XYZS (BaseAviary.py:194-197) and the orientation the client stores
-  s->init_tmpl.assign((size_t)s->D * 10, 0.0);
-  s->target.assign((size_t)s->D * 3, 0.0);
+  const size_t TE = s->het ? (size_t)s->E : 1;   // template / target tables: per env on a het sim
+  s->init_tmpl.assign(TE * s->D * 10, 0.0);
+  s->target.assign(TE * s->D * 3, 0.0);
+  if (s->het) {
+    s->epad = ((long long)s->E + 63) / 64 * 64;
+    s->het_xyz.resize((size_t)s->N * 3);
+    s->het_rpy.assign((size_t)s->N * 3, 0.0);
+    if (het->rows) s->env_rows.assign(het->rows, het->rows + s->E);
+    else s->env_rows.assign((size_t)s->E, env_row_of(P));
+  }
   for (int d = 0; d < s->D; ++d) {
     double xyz[3], rpy[3] = {0, 0, 0};
     if (C.init_xyzs_host) {
@@ -816,15 +1081,16 @@ int gpd_create(const gpd_drone_params* params, const gpd_config* cfg, gpd_sim** 
     }
     if (C.init_rpys_host)
       for (int k = 0; k < 3; ++k) rpy[k] = C.init_rpys_host[d * 3 + k];
-    double q0[4], qraw[4], qn[4], e[3];
-    h_quat_from_euler(rpy, q0);
-    h_roundtrip(q0, qraw);  // loadURDF stores the orientation through a btTransform
-    h_roundtrip(qraw, qn);  // readback (:517)
-    h_euler(qn, e);         // :518
-    double* t = &s->init_tmpl[(size_t)d * 10];
-    t[0] = xyz[0]; t[1] = xyz[1]; t[2] = xyz[2];
-    t[3] = qraw[0]; t[4] = qraw[1]; t[5] = qraw[2]; t[6] = qraw[3];
-    t[7] = e[0]; t[8] = e[1]; t[9] = e[2];
+    if (s->het) {   // cfg's pose for every env unless the per-env tables replace it (het_templates below)
+      for (int e = 0; e < s->E; ++e)
+        for (int k = 0; k < 3; ++k) {
+          const size_t i = ((size_t)e * s->D + d) * 3 + k;
+          s->het_xyz[i] = het->xyzs ? het->xyzs[i] : xyz[k];
+          s->het_rpy[i] = het->rpys ? het->rpys[i] : rpy[k];
+        }
+      continue;
+    }
+    pose_template(xyz, rpy, &s->init_tmpl[(size_t)d * 10]);
     if (C.task == GPD_TASK_HOVER) {           // HoverAviary.py:51
       s->target[d * 3 + 2] = 1.0;
     } else if (C.task == GPD_TASK_MULTIHOVER) {  // MultiHoverAviary.py:71
@@ -833,17 +1099,19 @@ int gpd_create(const gpd_drone_params* params, const gpd_config* cfg, gpd_sim** 
       s->target[d * 3 + 2] = xyz[2] + 1.0 / (d + 1);
     }
   }
+  if (s->het) het_templates(s);
 
   const size_t rs = real_size(s);
   hipError_t e1 = hipMalloc(&s->d_state, (size_t)kStateComps * s->npad * rs);
   hipError_t e2 = hipMalloc((void**)&s->d_ring, (size_t)s->ring_len * s->npad * s->A * sizeof(float));
   hipError_t e3 = hipMalloc((void**)&s->d_ctr, (size_t)(s->E + 1) * sizeof(int2));
-  hipError_t e4 = hipMalloc(&s->d_init, (size_t)s->D * 10 * rs);
-  hipError_t e5 = hipMalloc(&s->d_target, (size_t)s->D * 3 * rs);
+  hipError_t e4 = hipMalloc(&s->d_init, TE * s->D * 10 * rs);
+  hipError_t e5 = hipMalloc(&s->d_target, TE * s->D * 3 * rs);
   hipError_t e6 = hipMalloc(&s->d_consts, s->prec == GPD_F64 ? sizeof(Consts<double>) : sizeof(Consts<float>));
   hipError_t e7 = pid ? hipMalloc(&s->d_ctrl, (size_t)kCtrlComps * s->npad * rs) : hipSuccess;
+  hipError_t e8 = s->het ? hipMalloc(&s->d_etab, (size_t)kHetCols * s->epad * rs) : hipSuccess;
   if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess ||
-      e6 != hipSuccess || e7 != hipSuccess) {
+      e6 != hipSuccess || e7 != hipSuccess || e8 != hipSuccess) {
     free_sim(s);
     (void)hipGetLastError();
     return fail(GPD_ENOMEM, "gpd_create: hipMalloc failed");
@@ -884,6 +1152,7 @@ int gpd_create(const gpd_drone_params* params, const gpd_config* cfg, gpd_sim** 
     }
   }
   int rc = s->prec == GPD_F64 ? upload_tables<double>(s) : upload_tables<float>(s);
+  if (rc == GPD_OK && s->het) rc = s->prec == GPD_F64 ? upload_env_table<double>(s) : upload_env_table<float>(s);
   if (rc != GPD_OK) { free_sim(s); return rc; }
   if (hipMemset(s->d_state, 0, (size_t)kStateComps * s->npad * rs) != hipSuccess ||
       hipMemset(s->d_ring, 0, (size_t)s->ring_len * s->npad * s->A * sizeof(float)) != hipSuccess ||
@@ -898,6 +1167,10 @@ int gpd_create(const gpd_drone_params* params, const gpd_config* cfg, gpd_sim** 
   *out = s;
   return GPD_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int gpd_destroy(gpd_sim* sim) {
   if (!sim) return fail(GPD_EINVAL, "gpd_destroy: NULL sim");
@@ -966,6 +1239,9 @@ int gpd_cmd_step(gpd_sim* sim, int mode, const void* actions, void* obs20, void*
                                 " (GPD_CMD_RPM, GPD_CMD_VEL or GPD_CMD_WAYPOINT)");
   if (!sim) return fail(GPD_EINVAL, "gpd_cmd_step: NULL sim");
   if (!actions) return fail(GPD_EINVAL, "gpd_cmd_step: NULL actions");
+  if (sim->het)
+    return fail(GPD_EUNSUPPORTED, "gpd_cmd_step: not supported on a het sim (the command step kernels read the "
+                                  "sim-wide drone parameters)");
   if (mode != GPD_CMD_RPM && !sim->d_ctrl)
     return fail(GPD_EINVAL, "gpd_cmd_step: the VEL and WAYPOINT modes run DSLPIDControl, and the sim's action type "
                             "has no controller (create it with a PID action type)");

@@ -37,3 +37,4 @@
 #include "gpd_step_duo.h"
 #include "gpd_step_wide.h"
 #include "gpd_step_cmd.h"
+#include "gpd_step_het.h"

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from ..enums import ActionType, DroneModel, ObservationType, Physics
-from ..sim import BatchedAviarySim
+from ..sim import BatchedAviarySim, graph_capture
 from .spaces import action_space, observation_space
 
 
@@ -26,7 +26,7 @@ class AviaryVecEnv(_VecEnvBase):
     def __init__(self, num_envs, task="hover", num_drones=1, drone_model=DroneModel.CF2X, initial_xyzs=None,
                  initial_rpys=None, physics=Physics.DYN, aero=(), pyb_freq=240, ctrl_freq=30,
                  obs=ObservationType.KIN, act=ActionType.RPM, precision="f64", device=None, output="numpy",
-                 episode_len_sec=8, urdf_path=None, tuning=None):
+                 episode_len_sec=8, urdf_path=None, tuning=None, env_params=None):
         if ObservationType(obs) != ObservationType.KIN:
             raise NotImplementedError("ObservationType.RGB is out of scope")
         if output not in ("numpy", "torch"):
@@ -37,7 +37,7 @@ class AviaryVecEnv(_VecEnvBase):
                                     urdf_path=urdf_path, pyb_freq=pyb_freq, ctrl_freq=ctrl_freq, act=act,
                                     task=task, physics=physics, aero=aero, precision=precision, autoreset=True,
                                     episode_len_sec=episode_len_sec, initial_xyzs=initial_xyzs,
-                                    initial_rpys=initial_rpys, device=device, tuning=tuning)
+                                    initial_rpys=initial_rpys, device=device, tuning=tuning, env_params=env_params)
         self.num_envs = int(num_envs)
         self.num_drones = int(num_drones)
         self.output = output
@@ -117,7 +117,9 @@ class AviaryVecEnv(_VecEnvBase):
 
 def make_vec_env(env_cls, n_envs=1, seed=None, env_kwargs=None, distributed=False, **vec_kwargs):
     """``stable_baselines3.common.env_util.make_vec_env`` stand-in for the two RL aviaries:
-    builds ONE batched ``AviaryVecEnv`` instead of ``n_envs`` Python env objects; with
+    builds ONE batched ``AviaryVecEnv`` instead of ``n_envs`` Python env objects (``env_params`` and
+    (E, D, 3) ``initial_xyzs`` / ``initial_rpys`` in ``env_kwargs`` make its envs differ, as the
+    reference's env objects may; they need ``physics=Physics.DYN``, the default here is PYB); with
     ``distributed=True`` (inside an initialised torch.distributed group) a
     ``ShardedAviaryVecEnv`` whose envs are split over the group's ranks."""
     from .HoverAviary import HoverAviary
@@ -133,6 +135,11 @@ def make_vec_env(env_cls, n_envs=1, seed=None, env_kwargs=None, distributed=Fals
         kw.pop(k, None)
     kw.setdefault("physics", Physics.PYB)   # the env classes' default (HoverAviary.py:20, MultiHoverAviary.py:22)
     if distributed:
+        both = {**kw, **vec_kwargs}
+        if both.get("env_params") is not None or any(
+                both.get(k) is not None and np.ndim(both[k]) == 3 for k in ("initial_xyzs", "initial_rpys")):
+            raise NotImplementedError("per-env parameters and (E, D, 3) start poses are not supported by "
+                                      "ShardedAviaryVecEnv")
         return ShardedAviaryVecEnv(n_envs, task=task, num_drones=nd, **kw, **vec_kwargs)
     return AviaryVecEnv(n_envs, task=task, num_drones=nd, **kw, **vec_kwargs)
 
@@ -210,7 +217,7 @@ class ShardedAviaryVecEnv:
     def _replay_rollout(self, n_steps, seq):
         if self._rgraph is None:
             self._rgraph = torch.cuda.CUDAGraph()
-            with torch.cuda.device(self.sim.device), torch.cuda.graph(self._rgraph):
+            with graph_capture(self._rgraph, self.sim.device):
                 seq()
             self._rgraph_steps = n_steps
         elif n_steps != self._rgraph_steps:

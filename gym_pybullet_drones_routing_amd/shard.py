@@ -396,8 +396,9 @@ class LearnerHandoff:
             raise ValueError("a terminal_capacity below the shard size reads the finished count on the host "
                              "every step: not capturable")
         torch.cuda.synchronize(self.device)
+        from .sim import graph_capture
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.device(self.device), torch.cuda.graph(g):
+        with graph_capture(g, self.device):
             for _ in range(int(n_steps)):
                 self._step_body(self.global_actions if self.is_learner else None)
         if install:

@@ -5,7 +5,9 @@
 call enqueues HIP work on the current torch stream of the sim's device; nothing here
 computes physics on the CPU.
 """
+import contextlib
 import ctypes
+import gc
 import warnings
 
 import numpy as np
@@ -75,6 +77,26 @@ def physics_flags(physics=Physics.DYN, aero=()):
     return flags
 
 
+@contextlib.contextmanager
+def graph_capture(graph, device):
+    """``torch.cuda.graph(graph)`` on ``device`` with the cyclic garbage collector out of the way.
+
+    Under capture (torch's global capture mode) destroying a ``torch.cuda.CUDAGraph`` is an error,
+    and it is raised from the graph's destructor, which ends the process.  A graph held by a dead
+    reference cycle (an object whose closures refer back to it, say) is destroyed whenever the
+    cyclic collector next runs - possibly in the middle of a later capture; ``torch.cuda.graph``
+    no longer collects on entry.  So: collect before the capture, keep the collector off during it."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.device(device), torch.cuda.graph(graph):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
+
+
 def _stream(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
@@ -118,18 +140,70 @@ def pack_layout(n_envs, drones_per_env, obs_width, align=256):
     return out
 
 
+def env_param_rows(params, n_envs, env_params=None):
+    """``gpd_env_params`` rows [E, 11] float64 (column order ``_lib.ENV_PARAM_NAMES``): the values of
+    ``params`` (a ``_lib.DroneParams``) for every env, with the columns named in the dict
+    ``env_params`` ({name: array[E] or scalar}) replaced."""
+    rows = np.empty((int(n_envs), len(_lib.ENV_PARAM_NAMES)), dtype=np.float64)
+    for k, name in enumerate(_lib.ENV_PARAM_NAMES):
+        rows[:, k] = getattr(params, name)
+    unknown = set(env_params or ()) - set(_lib.ENV_PARAM_NAMES)
+    if unknown:
+        raise ValueError(f"unknown env_params names {sorted(unknown)}; expected a subset of "
+                         f"{list(_lib.ENV_PARAM_NAMES)}")
+    for name, val in (env_params or {}).items():
+        rows[:, _lib.ENV_PARAM_NAMES.index(name)] = np.broadcast_to(np.asarray(val, dtype=np.float64), (int(n_envs),))
+    return np.ascontiguousarray(rows)
+
+
+def _dptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+
+
+_DERIVED = ("gravity", "hover_rpm", "max_rpm", "max_thrust", "max_xy_torque", "max_z_torque", "gnd_eff_h_clip")
+
+
+def env_derive(params, rows):
+    """``gpd_env_derive`` (host-only): the derived constants of ``rows`` [n, 11] on the drone
+    ``params``, as a dict of [n] float64 arrays."""
+    rows = np.ascontiguousarray(np.asarray(rows, dtype=np.float64).reshape(-1, len(_lib.ENV_PARAM_NAMES)))
+    n = rows.shape[0]
+    out = (_lib.Constants * max(n, 1))()
+    _lib.check("gpd_env_derive", _lib.load().gpd_env_derive(ctypes.byref(params), _dptr(rows), n, out))
+    return {name: np.array([getattr(out[i], name) for i in range(n)], dtype=np.float64) for name in _DERIVED}
+
+
 class BatchedAviarySim:
-    """``n_envs`` x ``drones_per_env`` Crazyflie-class drones stepped in lockstep on one GPU."""
+    """``n_envs`` x ``drones_per_env`` Crazyflie-class drones stepped in lockstep on one GPU.
+
+    ``env_params`` ({name: array[E]} over any subset of ``_lib.ENV_PARAM_NAMES``) and / or
+    ``initial_xyzs`` / ``initial_rpys`` of shape (E, D, 3) make the sim heterogeneous (``sim.het``):
+    every env with its own drone parameters, every drone of every env with its own start pose
+    (``gpd_create_het``).  Het sims run Physics.DYN (with any of the gnd / drag / dw / geom terms) and
+    the RPM action types; anything else raises NotImplementedError."""
 
     def __init__(self, n_envs, drones_per_env=1, drone_model=DroneModel.CF2X, urdf_path=None,
                  pyb_freq=240, ctrl_freq=30, act=ActionType.RPM, task="hover",
                  physics=Physics.DYN, aero=(), precision="f64", autoreset=True, episode_len_sec=8,
-                 initial_xyzs=None, initial_rpys=None, device=None, tuning=None):
+                 initial_xyzs=None, initial_rpys=None, device=None, tuning=None, env_params=None):
         self._lib = _lib.load()
+        act = ActionType(act)
+        if env_params is not None or any(a is not None and np.ndim(a) == 3 for a in (initial_xyzs, initial_rpys)):
+            # a heterogeneous sim: what it cannot run is refused, never silently dropped
+            if physics_flags(physics, aero) & _lib.GPD_F_BULLET:
+                raise NotImplementedError(
+                    f"per-env parameters / start poses with {Physics(physics)}"
+                    f"{' + bullet' if 'bullet' in aero else ''}: the PYB* contact solves hold mass and inertia in "
+                    "derived rows; pass physics=Physics.DYN (aero terms gnd / drag / dw / geom are supported)")
+            if act in PID_ACTS:
+                raise NotImplementedError(f"per-env parameters / start poses with {act}: DSLPIDControl is tuned for "
+                                          "the nominal drone; use ActionType.RPM or ActionType.ONE_D_RPM")
+            if int(drones_per_env) > 64:
+                raise NotImplementedError("per-env parameters / start poses need drones_per_env <= 64 (the "
+                                          "multi-wave step kernel has no per-env parameters)")
         if not torch.cuda.is_available():
             raise _lib.GpdLibraryError("BatchedAviarySim needs a ROCm GPU (torch.cuda.is_available() is False)")
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
-        act = ActionType(act)
         if precision not in ("f32", "f64"):
             raise ValueError("precision must be 'f32' or 'f64'")
         if precision == "f32":
@@ -172,16 +246,32 @@ class BatchedAviarySim:
                 raise ValueError(f"unknown tuning field {name!r}")
             setattr(cfg, name, int(val))
         keep = []
+        het_poses = {}
         for name, arr in (("init_xyzs_host", initial_xyzs), ("init_rpys_host", initial_rpys)):
             if arr is not None:
-                a = np.ascontiguousarray(np.asarray(arr, dtype=np.float64).reshape(self.drones_per_env, 3))
+                a = np.asarray(arr, dtype=np.float64)
+                if a.ndim == 3:      # (E, D, 3): per-env start poses
+                    het_poses[name] = self._pose_table(a)
+                    continue
+                a = np.ascontiguousarray(a.reshape(self.drones_per_env, 3))
                 keep.append(a)
                 setattr(cfg, name, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
         self.physics_flags = cfg.physics_flags
+        self.het = env_params is not None or bool(het_poses)
         handle = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check("gpd_create", self._lib.gpd_create(ctypes.byref(self.params), ctypes.byref(cfg),
-                                                          ctypes.byref(handle)))
+        if self.het:
+            self._env_rows = env_param_rows(self.params, self.n_envs, env_params)
+            with torch.cuda.device(self.device):
+                rc = self._lib.gpd_create_het(ctypes.byref(self.params), ctypes.byref(cfg), _dptr(self._env_rows),
+                                              _dptr(het_poses.get("init_xyzs_host")),
+                                              _dptr(het_poses.get("init_rpys_host")), ctypes.byref(handle))
+            if rc == _lib.GPD_EUNSUPPORTED:
+                raise NotImplementedError(self._lib.gpd_last_error().decode(errors="replace"))
+            _lib.check("gpd_create_het", rc)
+        else:
+            with torch.cuda.device(self.device):
+                _lib.check("gpd_create", self._lib.gpd_create(ctypes.byref(self.params), ctypes.byref(cfg),
+                                                              ctypes.byref(handle)))
         self._h = handle
         k = _lib.Constants()
         _lib.check("gpd_get_constants", self._lib.gpd_get_constants(self._h, ctypes.byref(k)))
@@ -211,6 +301,54 @@ class BatchedAviarySim:
         self._tobs_ptr = _ptr(self.terminal_obs)
         self._obs20 = None              # cmd_step's [E, D, 20] rows, allocated on first use (not in out_pack)
         self.reset()
+
+    # ------------------------------------------------------------------ heterogeneous sims
+    def _pose_table(self, arr):
+        a = np.asarray(arr, dtype=np.float64)
+        if a.shape != (self.n_envs, self.drones_per_env, 3):
+            raise ValueError(f"per-env poses must have shape ({self.n_envs}, {self.drones_per_env}, 3), got {a.shape}")
+        return np.ascontiguousarray(a)
+
+    def _need_het(self, what):
+        if not self.het:
+            raise ValueError(f"{what} needs a heterogeneous sim: create it with env_params= or (E, D, 3) start poses")
+
+    def set_env_params(self, env_params):
+        """Replace the per-env drone parameters (``gpd_set_env_params``): ``env_params`` is a dict
+        {name: array[E]}; names it leaves out keep their current per-env values.  A synchronous
+        upload that changes no launch geometry: a captured graph stays valid.  Acts from the next step."""
+        self._need_het("set_env_params")
+        rows = self._env_rows.copy()
+        fresh = env_param_rows(self.params, self.n_envs, env_params)
+        for name in env_params:
+            k = _lib.ENV_PARAM_NAMES.index(name)
+            rows[:, k] = fresh[:, k]
+        with torch.cuda.device(self.device):
+            self._call("gpd_set_env_params", _dptr(rows))
+        self._env_rows = rows
+
+    def set_initial_poses(self, xyzs=None, rpys=None):
+        """Replace the per-env start poses (``gpd_set_env_init``), each (E, D, 3) or None to keep.
+        They take effect at the next reset or auto-reset; MultiHover targets follow them."""
+        self._need_het("set_initial_poses")
+        x = self._pose_table(xyzs) if xyzs is not None else None
+        r = self._pose_table(rpys) if rpys is not None else None
+        with torch.cuda.device(self.device):
+            self._call("gpd_set_env_init", _dptr(x), _dptr(r))
+
+    @property
+    def env_params(self):
+        """The current per-env parameters as {name: array[E]} (every env nominal on a plain sim)."""
+        rows = self._env_rows if self.het else env_param_rows(self.params, self.n_envs)
+        return {name: rows[:, k].copy() for k, name in enumerate(_lib.ENV_PARAM_NAMES)}
+
+    @property
+    def env_constants(self):
+        """Per-env derived constants (BaseAviary.py:117-128) from ``gpd_env_derive``: a dict of [E]
+        float64 arrays (gravity, hover_rpm, max_rpm, max_thrust, max_xy_torque, max_z_torque,
+        gnd_eff_h_clip)."""
+        rows = self._env_rows if self.het else env_param_rows(self.params, self.n_envs)
+        return env_derive(self.params, rows)
 
     def _field(self, name, dtype, shape):
         off, n = self.pack_layout[name]
@@ -293,7 +431,7 @@ class BatchedAviarySim:
                 raise ValueError("capture_graph needs contiguous float32 action tensors on the sim's device")
             seq.append(a)
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.device(self.device), torch.cuda.graph(g):
+        with graph_capture(g, self.device):
             for a in seq:
                 self.step(a, terminal_obs=terminal_obs)
         return g
@@ -323,6 +461,9 @@ class BatchedAviarySim:
             a = torch.as_tensor(a, dtype=dtype, device=self.device).contiguous()
         if a.numel() != self.n_drones * width:
             raise ValueError(f"actions must have {self.n_envs}x{self.drones_per_env}x{width} elements")
+        if self.het:
+            raise NotImplementedError("cmd_step is not supported on a heterogeneous sim (the command step kernels "
+                                      "read the sim-wide drone parameters)")
         with torch.cuda.device(self.device):
             self._call("gpd_cmd_step", code, _ptr(a), _ptr(self._cmd_rows()), _stream(self.device))
         return self._obs20
@@ -346,7 +487,7 @@ class BatchedAviarySim:
                 raise ValueError(f"capture_cmd_graph needs contiguous {dtype} action tensors on the sim's device")
         self._cmd_rows()    # allocated outside the capture
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.device(self.device), torch.cuda.graph(g):
+        with graph_capture(g, self.device):
             for a in actions_seq:
                 self.cmd_step(a, mode)
         return g

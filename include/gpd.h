@@ -178,6 +178,57 @@ int gpd_create(const gpd_drone_params* params, const gpd_config* cfg, gpd_sim** 
 int gpd_destroy(gpd_sim* sim);
 int gpd_get_constants(const gpd_sim* sim, gpd_constants* out);
 
+/* ---- Heterogeneous ("het") sims: per-env drone parameters and per-env start poses, what the
+ * reference's vector of env objects allows (each parses its own URDF and takes its own
+ * initial_xyzs / initial_rpys, BaseAviary.py:97-128, :194-207, :982-1014).
+ *
+ * The per-env part of gpd_drone_params: 11 doubles per env.  Everything else (model, prop_pos,
+ * prop_radius, dw_coeff_1..3, the collision fields, max_speed_kmh) stays sim-wide, from the
+ * gpd_drone_params passed at create. */
+typedef struct gpd_env_params {
+  double m, arm, thrust2weight, ixx, iyy, izz, kf, km, gnd_eff_coeff, drag_coeff_xy, drag_coeff_z;
+} gpd_env_params;
+
+/* gpd_create with per-env tables (all host memory, copied):
+ *   env_params_host [E]        NULL = every env takes `params`
+ *   init_xyzs_host  [E][D][3]  NULL = cfg's INIT_XYZS for every env
+ *   init_rpys_host  [E][D][3]  NULL = cfg's INIT_RPYS for every env
+ * All envs share cfg (physics flags, action type, task, frequencies).  One launch per gpd_step,
+ * as on a plain sim.  Supported: the DYN integrator with any subset of GPD_F_GND | GPD_F_DRAG |
+ * GPD_F_DW | GPD_F_GEOM_WRENCH, GPD_ACT_RPM / GPD_ACT_ONE_D_RPM, every task, both precisions,
+ * drones_per_env <= 64 with an observation row that fits the one-wave kernel's LDS tile.
+ * GPD_EUNSUPPORTED (the message names the reason): GPD_F_BULLET (the contact solves hold mass and
+ * inertia in many derived rows), the PID action types, drones_per_env > 64 or a longer action
+ * history; gpd_cmd_step on a het sim.  No physics term is dropped silently.
+ * Every check runs before the first device call: each row's fields must be finite and > 0
+ * (>= 0 for gnd_eff_coeff, drag_coeff_xy, drag_coeff_z), each pose finite; a failure's message
+ * names the field and the env index.
+ * MultiHover targets are each env's INIT_XYZS + (0,0,1/(i+1)) (MultiHoverAviary.py:71); the hover
+ * target stays (0,0,1).  gpd_get_constants reports the constants of `params` (the nominal drone)
+ * and lanes_per_block 64; gpd_env_derive gives the per-env ones.
+ * The checkpoint blob (gpd_save_state) does not carry the tables: after gpd_load_state into
+ * another sim, re-apply them with gpd_set_env_params / gpd_set_env_init. */
+int gpd_create_het(const gpd_drone_params* params, const gpd_config* cfg, const gpd_env_params* env_params_host,
+                   const double* init_xyzs_host, const double* init_rpys_host, gpd_sim** out);
+
+/* Het sims only (GPD_EINVAL otherwise): replace every env's parameters (rows_host [E], validated
+ * as at create) / start poses (xyzs_host, rpys_host [E][D][3]; NULL keeps the current table).
+ * Synchronous uploads, like gpd_set_pid_params; launch geometry never changes, so a captured
+ * graph stays valid.  gpd_set_env_params first writes back a last_clipped_action that is still
+ * held in the action ring (it is rebuilt from the env's hover RPM: the old one, which the steps
+ * applied).  New parameters act from the next step; new start poses (and the MultiHover
+ * targets that follow them) from the next reset or auto-reset. */
+int gpd_set_env_params(gpd_sim* sim, const gpd_env_params* rows_host);
+int gpd_set_env_init(gpd_sim* sim, const double* xyzs_host, const double* rpys_host);
+
+/* Host-only and pure: the derived constants of n env rows on the drone `base` (its model selects
+ * the max_xy_torque formula, its prop_radius enters gnd_eff_h_clip), exactly as BaseAviary.py:117-128
+ * computes them: gravity, hover_rpm, max_rpm, max_thrust, max_xy_torque, max_z_torque,
+ * gnd_eff_h_clip of out[i]; the other fields of out[i] are 0.  MAX_RPM**2 is evaluated as Python
+ * does, with libm's pow(x, 2.0), which can differ from x*x (what gpd_create's gpd_get_constants
+ * uses) in the last bit; a het sim's ground-effect clip height is this function's value. */
+int gpd_env_derive(const gpd_drone_params* base, const gpd_env_params* rows, int n, gpd_constants* out);
+
 /* reset(): envs with env_mask[e] != 0 (env_mask == NULL: all envs) go back to INIT_XYZS /
  * INIT_RPYS with zero velocities, step_counter 0, last_clipped_action 0.  The action ring is
  * NOT cleared (the reference never clears action_buffer).  If obs != NULL the reset
