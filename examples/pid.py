@@ -3,7 +3,7 @@ E envs at once, no plotting).
 
 Every drone of every env follows its own phase of a horizontal circle at its initial height:
 one ``cmd_step(..., "waypoint")`` launch per control step runs the controller and the physics
-substeps of all E x D drones.  The waypoints of the whole flight are built on the device up
+substeps of all E x D drones; with ``--fused`` one ``cmd_rollout`` call flies the whole flight.  The waypoints of the whole flight are built on the device up
 front; env 0 is logged through ``Logger`` (saved as .npy and CSV under ``--output_folder``).
 
     python examples/pid.py --num_envs 256 --num_drones 3 --duration_sec 4
@@ -23,7 +23,7 @@ from gym_pybullet_drones_routing_amd.sim import BatchedAviarySim  # noqa: E402
 
 
 def run(num_envs=256, num_drones=3, drone=DroneModel.CF2X, physics=Physics.PYB, pyb_freq=240, ctrl_freq=48,
-        duration_sec=4.0, radius=0.3, period_sec=10.0, output_folder="results", save=True):
+        duration_sec=4.0, radius=0.3, period_sec=10.0, output_folder="results", save=True, fused=False):
     E, D = int(num_envs), int(num_drones)
     # the drones start on the circle, a sixth of a turn and 5 cm of height apart
     phase0 = np.arange(D) * (2 * np.pi / 6)
@@ -47,20 +47,32 @@ def run(num_envs=256, num_drones=3, drone=DroneModel.CF2X, physics=Physics.PYB, 
     wp[..., 3] = torch.as_tensor(init_rpys[:, 2], device=dev)
     logger = Logger(logging_freq_hz=ctrl_freq, num_drones=D, output_folder=output_folder, duration_sec=duration_sec,
                     device=dev)
-    controls = torch.zeros((D, 12), dtype=torch.float64, device=dev)
     torch.cuda.synchronize(dev)
     start = time.time()
-    for i in range(steps):
-        obs = sim.cmd_step(wp[i], "waypoint")
-        controls[:, 0:3] = wp[i, 0, :, 0:3]          # the logged control: target position, target rpy
-        controls[:, 5] = wp[i, 0, :, 3]
-        logger.log_batch(i / ctrl_freq, obs[0], controls)
+    if fused:
+        # the whole flight in one call: the controller and the physics of every step on the device,
+        # env 0's recorded rows logged in one go
+        traj, obs, metrics = sim.cmd_rollout(wp, "waypoint", metrics=True)
+        controls = torch.zeros((steps, D, 12), dtype=torch.float64, device=dev)
+        controls[:, :, 0:3] = wp[:, 0, :, 0:3]
+        controls[:, :, 5] = wp[:, 0, :, 3]
+        logger.log_rollout(0.0, 1.0 / ctrl_freq, traj[:, 0], controls)
+    else:
+        controls = torch.zeros((D, 12), dtype=torch.float64, device=dev)
+        for i in range(steps):
+            obs = sim.cmd_step(wp[i], "waypoint")
+            controls[:, 0:3] = wp[i, 0, :, 0:3]          # the logged control: target position, target rpy
+            controls[:, 5] = wp[i, 0, :, 3]
+            logger.log_batch(i / ctrl_freq, obs[0], controls)
     torch.cuda.synchronize(dev)
     wall = time.time() - start
     err = (obs[..., 0:3] - wp[-1, ..., 0:3]).norm(dim=-1)
     print(f"[pid] {E} envs x {D} drones, {steps} control steps in {wall:.2f} s "
           f"({E * D * steps / wall:.0f} drone-steps/s); final tracking error mean {float(err.mean()):.4f} m, "
           f"max {float(err.max()):.4f} m; adjacency (r = 10 m) of env 0:\n{sim.adjacency(10.0)[0].cpu().numpy()}")
+    if fused:
+        rms = torch.sqrt(metrics[..., 0].mean() / steps)
+        print(f"[pid] tracking error over the flight: RMS {float(rms):.4f} m, max {float(metrics[..., 1].max()):.4f} m")
     if save:
         print("[pid] saved", logger.save())
         logger.save_as_csv("pid")
@@ -79,6 +91,7 @@ if __name__ == "__main__":
     ap.add_argument("--ctrl_freq", default=48, type=int)
     ap.add_argument("--duration_sec", default=4.0, type=float)
     ap.add_argument("--output_folder", default="results")
+    ap.add_argument("--fused", action="store_true", help="fly the whole flight with one cmd_rollout call")
     a = ap.parse_args()
     run(a.num_envs, a.num_drones, a.drone, a.physics, a.pyb_freq, a.ctrl_freq, a.duration_sec,
-        output_folder=a.output_folder)
+        output_folder=a.output_folder, fused=a.fused)

@@ -36,7 +36,8 @@ EXPORTED = ("gpd_abi_version", "gpd_last_error", "gpd_default_params", "gpd_crea
             "gpd_get_raw_state", "gpd_set_raw_state", "gpd_get_step_counters",
             "gpd_set_step_counters", "gpd_state_bytes", "gpd_save_state", "gpd_load_state",
             "gpd_default_pid_params", "gpd_set_pid_params", "gpd_get_ctrl_state", "gpd_set_ctrl_state",
-            "gpd_nonfinite", "gpd_cmd_step", "gpd_adjacency", "gpd_pack_layout_of", "gpd_handoff_pack", "gpd_handoff_unpack",
+            "gpd_nonfinite", "gpd_cmd_step", "gpd_cmd_rollout", "gpd_adjacency", "gpd_pack_layout_of", "gpd_handoff_pack",
+            "gpd_handoff_unpack",
             "gpd_create_het", "gpd_set_env_params", "gpd_set_env_init", "gpd_env_derive")
 
 # gpd_env_params: the per-env part of the drone parameters, in the struct's field order
@@ -141,6 +142,7 @@ def load():
         "gpd_set_ctrl_state": (ci, [vp, vp, vp]),
         "gpd_nonfinite": (ci, [vp, vp, vp]),
         "gpd_cmd_step": (ci, [vp, i, vp, vp, vp]),
+        "gpd_cmd_rollout": (ci, [vp, i, vp, i, i, vp, vp, vp, i, vp]),
         "gpd_adjacency": (ci, [vp, ctypes.c_double, vp, vp]),
         "gpd_pack_layout_of": (ci, [i, i, i, ctypes.POINTER(PackLayout)]),
         "gpd_handoff_pack": (ci, [vp, ctypes.POINTER(PackLayout), vp]),

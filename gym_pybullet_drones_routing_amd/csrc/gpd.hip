@@ -559,6 +559,66 @@ int launch_cmd_step(gpd_sim* s, int mode, const void* actions, void* obs20, hipS
   return GPD_OK;
 }
 
+// gpd_cmd_rollout: cmd_step_fn's instantiations of the multi-step kernel.
+template <typename R>
+const void* cmd_rollout_fn(bool multi, bool plain, bool ctrl) {
+  if (ctrl)
+    return multi ? (const void*)cmd_rollout_kernel<R, true, kPfRuntime, true>
+                 : (const void*)cmd_rollout_kernel<R, false, kPfRuntime, true>;
+  if (multi)
+    return plain ? (const void*)cmd_rollout_kernel<R, true, 0, false>
+                 : (const void*)cmd_rollout_kernel<R, true, kPfRuntime, false>;
+  return plain ? (const void*)cmd_rollout_kernel<R, false, 0, false>
+               : (const void*)cmd_rollout_kernel<R, false, kPfRuntime, false>;
+}
+
+template <typename R>
+int launch_cmd_rollout(gpd_sim* s, int mode, const void* actions, int n_steps, int record_every, void* traj,
+                       void* obs20, void* metrics, int chunk, hipStream_t st) {
+  const size_t row_bytes = (size_t)s->N * (mode == GPD_CMD_WAYPOINT ? 7 : 4) *
+                           (mode == GPD_CMD_VEL ? sizeof(float) : sizeof(R));   // one step's commands
+  const size_t rows20 = (size_t)s->N * 20;
+  const char* act = (const char*)actions;
+  R* tr = (R*)traj;
+  R* m = (R*)metrics;
+  if (s->D > kWave) {
+    // envs of 65 .. 1024 drones: the command step's own wide kernel, one launch per step, storing a
+    // recorded step's rows straight into traj; the tracking figures from a pass over the stored
+    // positions behind every step
+    const SimView<R> v = make_view<R>(s);
+    for (int t = 0; t < n_steps; ++t) {
+      const int g = t + 1;
+      const bool rec = tr && g % record_every == 0, last = g == n_steps;
+      R* dst = rec ? tr + (size_t)(g / record_every - 1) * rows20 : (last ? (R*)obs20 : nullptr);
+      const int rc = launch_cmd_step<R>(s, mode, act + (size_t)t * row_bytes, dst, st);
+      if (rc != GPD_OK) return rc;
+      if (rec && last && obs20)
+        HIP_TRY(hipMemcpyAsync(obs20, dst, rows20 * sizeof(R), hipMemcpyDeviceToDevice, st));
+      if (m) {
+        hipLaunchKernelGGL((cmd_track_kernel<R>), dim3(grid_for(s->N, 256)), dim3(256), 0, st, v,
+                           (const R*)(act + (size_t)t * row_bytes), m, t > 0 ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+      }
+    }
+    return GPD_OK;
+  }
+  const SimView<R> v = make_view<R>(s);
+  const Consts<R>* c = (const Consts<R>*)s->d_consts;
+  const void* f = cmd_rollout_fn<R>(s->D > 1, s->cfg.physics_flags == 0, mode != GPD_CMD_RPM);
+  R max_rpm = (R)s->K.max_rpm;
+  for (int t0 = 0; t0 < n_steps; t0 += chunk) {
+    int n = n_steps - t0 < chunk ? n_steps - t0 : chunk;
+    const void* a = act + (size_t)t0 * row_bytes;
+    int rec_phase = t0 % record_every, carry = t0 > 0 ? 1 : 0;
+    long long rec_row = t0 / record_every;
+    R* o = t0 + n == n_steps ? (R*)obs20 : nullptr;
+    void* args[] = {(void*)&v, (void*)&c, (void*)&a, (void*)&mode, (void*)&max_rpm, (void*)&n, (void*)&record_every,
+                    (void*)&rec_phase, (void*)&rec_row, (void*)&tr, (void*)&o, (void*)&m, (void*)&carry};
+    HIP_TRY(hipLaunchKernel(f, dim3(grid_for(s->N, s->tpb)), dim3(kWave), args, 0, st));
+  }
+  return GPD_OK;
+}
+
 template <typename R>
 int launch_adjacency(gpd_sim* s, double radius, uint8_t* out, hipStream_t st) {
   const SimView<R> v = make_view<R>(s);
@@ -1252,6 +1312,39 @@ int gpd_cmd_step(gpd_sim* sim, int mode, const void* actions, void* obs20, void*
   hipStream_t st = (hipStream_t)stream;
   return sim->prec == GPD_F64 ? launch_cmd_step<double>(sim, mode, actions, obs20, st)
                               : launch_cmd_step<float>(sim, mode, actions, obs20, st);
+}
+
+int gpd_cmd_rollout(gpd_sim* sim, int mode, const void* actions, int n_steps, int record_every, void* traj,
+                    void* obs20, void* metrics, int max_steps_per_launch, void* stream) {
+  if (mode != GPD_CMD_RPM && mode != GPD_CMD_VEL && mode != GPD_CMD_WAYPOINT)
+    return fail(GPD_EINVAL, "gpd_cmd_rollout: unknown mode " + std::to_string(mode) +
+                                " (GPD_CMD_RPM, GPD_CMD_VEL or GPD_CMD_WAYPOINT)");
+  if (n_steps < 0) return fail(GPD_EINVAL, "gpd_cmd_rollout: n_steps < 0");
+  if (record_every < 1) return fail(GPD_EINVAL, "gpd_cmd_rollout: record_every must be >= 1");
+  if (max_steps_per_launch < 0)
+    return fail(GPD_EINVAL, "gpd_cmd_rollout: max_steps_per_launch must be 0 (the default, 256) or >= 1");
+  if (!sim) return fail(GPD_EINVAL, "gpd_cmd_rollout: NULL sim");
+  if (n_steps > 0 && !actions) return fail(GPD_EINVAL, "gpd_cmd_rollout: NULL actions");
+  if (sim->het)
+    return fail(GPD_EUNSUPPORTED, "gpd_cmd_rollout: not supported on a het sim (the command step kernels read the "
+                                  "sim-wide drone parameters)");
+  if (mode != GPD_CMD_RPM && !sim->d_ctrl)
+    return fail(GPD_EINVAL, "gpd_cmd_rollout: the VEL and WAYPOINT modes run DSLPIDControl, and the sim's action "
+                            "type has no controller (create it with a PID action type)");
+  if (metrics && mode != GPD_CMD_WAYPOINT)
+    return fail(GPD_EINVAL, "gpd_cmd_rollout: metrics needs GPD_CMD_WAYPOINT (the tracking error is measured "
+                            "against the waypoint rows' target positions)");
+  if (mode != GPD_CMD_WAYPOINT && actions && !aligned16(actions))
+    return fail(GPD_EINVAL, "gpd_cmd_rollout: actions must be 16-byte aligned");
+  if (traj && !aligned16(traj)) return fail(GPD_EINVAL, "gpd_cmd_rollout: traj must be 16-byte aligned");
+  if (obs20 && !aligned16(obs20)) return fail(GPD_EINVAL, "gpd_cmd_rollout: obs20 must be 16-byte aligned");
+  if (metrics && !aligned16(metrics)) return fail(GPD_EINVAL, "gpd_cmd_rollout: metrics must be 16-byte aligned");
+  if (n_steps == 0) return GPD_OK;
+  const int chunk = max_steps_per_launch == 0 ? 256 : max_steps_per_launch;
+  hipStream_t st = (hipStream_t)stream;
+  return sim->prec == GPD_F64
+             ? launch_cmd_rollout<double>(sim, mode, actions, n_steps, record_every, traj, obs20, metrics, chunk, st)
+             : launch_cmd_rollout<float>(sim, mode, actions, n_steps, record_every, traj, obs20, metrics, chunk, st);
 }
 
 int gpd_adjacency(gpd_sim* sim, double radius, uint8_t* out, void* stream) {

@@ -37,4 +37,5 @@
 #include "gpd_step_duo.h"
 #include "gpd_step_wide.h"
 #include "gpd_step_cmd.h"
+#include "gpd_step_rollout.h"
 #include "gpd_step_het.h"

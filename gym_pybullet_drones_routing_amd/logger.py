@@ -94,6 +94,38 @@ class Logger:
             self._ct[c] = torch.as_tensor(controls).to(device=self.device, dtype=self.dtype).reshape(self.NUM_DRONES, 12)
         self.counters[:] = c + 1
 
+    def log_rollout(self, t0, dt, states, controls=None):
+        """Equivalent to ``log_batch(t0 + k * dt, states[k], controls[k])`` for k = 0..T-1 as one
+        device write per array: ``states`` [T, D, 20] (e.g. a drone slice of ``cmd_rollout``'s
+        trajectory), ``controls`` [T, D, 12] or None.  The capacity grows once."""
+        s = torch.as_tensor(states).to(device=self.device, dtype=self.dtype).reshape(-1, self.NUM_DRONES, 20)
+        T = s.shape[0]
+        if T == 0:
+            return
+        c = int(self.counters[0])
+        if not np.all(self.counters == c):      # per-drone counters apart: log()'s own rules, row by row
+            for k in range(T):
+                self.log_batch(t0 + k * dt, states[k], None if controls is None else controls[k])
+            return
+        # the row of the first call (log_batch); every later call finds counter == width or, past a
+        # preallocated width, grows by one: consecutive rows either way
+        if c < self._width and not self.PREALLOCATED_ARRAYS:
+            c = self._width - 1
+        end = c + T
+        if end > self._ts.shape[0]:
+            self._alloc(max(end, 2 * self._ts.shape[0]))
+        self._width = max(self._width, end)
+        # t0 + k * dt in float64 on the host: the very doubles the log_batch loop would pass
+        ts = torch.from_numpy(t0 + np.arange(T, dtype=np.float64) * dt).to(device=self.device, dtype=self.dtype)
+        self._ts[c:end] = ts.reshape(T, 1)
+        self._st[c:end] = s.index_select(2, self._idx)
+        if controls is None:
+            self._ct[c:end] = 0
+        else:
+            self._ct[c:end] = torch.as_tensor(controls).to(device=self.device, dtype=self.dtype).reshape(
+                T, self.NUM_DRONES, 12)
+        self.counters[:] = end
+
     @property
     def timestamps(self):
         return self._ts[:self._width].transpose(0, 1).cpu().numpy()

@@ -492,6 +492,46 @@ class BatchedAviarySim:
                 self.cmd_step(a, mode)
         return g
 
+    def cmd_rollout(self, actions, mode="rpm", record_every=1, record=True, metrics=False, max_steps_per_launch=0):
+        """``T`` consecutive :meth:`cmd_step` calls with the on-device controller in the loop, in one
+        launch per ``max_steps_per_launch`` steps (``gpd_cmd_rollout``; 0 = the library's default of
+        256): the drones stay in registers between the steps.  ``actions`` [T, E, D, w] with
+        ``cmd_step``'s widths and dtypes for ``mode``.
+
+        Returns ``(traj, obs20, metrics)``: ``traj`` [T // record_every, E, D, 20], the state vectors
+        after steps ``record_every``, ``2 * record_every``, ... (None with ``record=False``);
+        ``obs20`` the sim-owned [E, D, 20] buffer ``cmd_step`` returns, holding the last step's rows;
+        ``metrics`` [E, D, 2] (``"waypoint"`` only, None unless asked for): the sum over the steps
+        of the squared distance to the step's target position, and the largest distance.  ``traj``
+        and ``metrics`` are fresh tensors.  The sim ends exactly where T ``cmd_step`` calls leave it."""
+        try:
+            code, width, real = _CMD_MODES[mode]
+        except KeyError:
+            raise ValueError(f"mode must be one of {sorted(_CMD_MODES)}, got {mode!r}") from None
+        dtype = self.real_dtype if real else torch.float32
+        a = actions
+        if not (isinstance(a, torch.Tensor) and a.device == self.device and a.dtype == dtype and a.is_contiguous()):
+            a = torch.as_tensor(a, dtype=dtype, device=self.device).contiguous()
+        per = self.n_drones * width
+        if a.dim() < 1 or a.numel() != a.shape[0] * per:
+            raise ValueError(f"actions must have Tx{self.n_envs}x{self.drones_per_env}x{width} elements")
+        T, E, D = int(a.shape[0]), self.n_envs, self.drones_per_env
+        if int(record_every) < 1:
+            raise ValueError(f"record_every must be >= 1, got {record_every}")
+        if metrics and mode != "waypoint":
+            raise ValueError("metrics=True needs mode='waypoint' (the tracking error is measured against the "
+                             "waypoints' target positions)")
+        if self.het:
+            raise NotImplementedError("cmd_rollout is not supported on a heterogeneous sim (the command step kernels "
+                                      "read the sim-wide drone parameters)")
+        traj = torch.empty((T // int(record_every), E, D, 20), dtype=self.real_dtype, device=self.device) \
+            if record else None
+        met = torch.zeros((E, D, 2), dtype=self.real_dtype, device=self.device) if metrics else None
+        with torch.cuda.device(self.device):
+            self._call("gpd_cmd_rollout", code, _ptr(a), T, int(record_every), _ptr(traj), _ptr(self._cmd_rows()),
+                       _ptr(met), int(max_steps_per_launch), _stream(self.device))
+        return traj, self._obs20, met
+
     def adjacency(self, radius=np.inf):
         """BaseAviary._getAdjacencyMatrix (:658-675) of every env: [E, D, D] uint8 on the device."""
         out = torch.empty((self.n_envs, self.drones_per_env, self.drones_per_env), dtype=torch.uint8,

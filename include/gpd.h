@@ -275,6 +275,29 @@ int gpd_integrate(gpd_sim* sim, const void* rpm, int n_sub, void* traj, void* st
 #define GPD_CMD_WAYPOINT 2
 int gpd_cmd_step(gpd_sim* sim, int mode, const void* actions, void* obs20, void* stream);
 
+/* The closed-loop rollout: n_steps consecutive gpd_cmd_step calls in (at most)
+ * ceil(n_steps / max_steps_per_launch) launches.  A block keeps its drones, their controller state
+ * and last_clipped_action in registers between the steps of a launch; the state, the controller
+ * state, last_clipped_action and the step counters (+= n_steps * PYB_STEPS_PER_CTRL) end exactly
+ * where n_steps gpd_cmd_step calls leave them, the action ring of the RL step is untouched.
+ *   actions [n_steps][N][w]  as gpd_cmd_step's for `mode` (w = 4, 4, 7; same dtypes, the same
+ *                            16-byte rule for the base pointer of RPM / VEL rows)
+ *   record_every >= 1; traj (nullable) [n_steps / record_every][N][20] real: the state20 rows after
+ *                            steps record_every, 2*record_every, ... (1-based): what gpd_cmd_step's
+ *                            obs20 would have held after those steps
+ *   obs20 (nullable) [N][20] real: the rows after the last step
+ *   metrics (nullable, GPD_CMD_WAYPOINT only, else GPD_EINVAL) [N][2] real: the sum over the steps
+ *                            of |pos_after_step - target_pos_of_that_step|^2 and the max over the
+ *                            steps of that distance, accumulated in step order in the sim's real type
+ *   max_steps_per_launch     0 = default (256), else >= 1.  Launches continue one another exactly
+ *                            (the state passes through memory in the sim's own type, metrics carry on).
+ * traj, obs20 and metrics must be 16-byte aligned.  n_steps == 0 succeeds and writes nothing.
+ * Asynchronous on `stream`, fixed-argument launches (graph-capturable), no host state.
+ * Envs of more than 64 drones run one gpd_cmd_step launch per step from native code (the same
+ * results).  GPD_EUNSUPPORTED on a het sim, as gpd_cmd_step. */
+int gpd_cmd_rollout(gpd_sim* sim, int mode, const void* actions, int n_steps, int record_every, void* traj,
+                    void* obs20, void* metrics, int max_steps_per_launch, void* stream);
+
 /* BaseAviary._getAdjacencyMatrix (:658-675) of every env: out [E][D][D] uint8 (device memory),
  * 1 on the diagonal and where |pos_i - pos_j| < radius (radius = inf: all ones). */
 int gpd_adjacency(gpd_sim* sim, double radius, uint8_t* out, void* stream);
