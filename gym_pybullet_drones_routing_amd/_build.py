@@ -14,6 +14,12 @@ LIB_PATH = PKG_DIR / "libgpd.so"
 # every header and source under csrc/: a header added later cannot be missed by needs_build()
 SOURCES = sorted(CSRC.glob("*.h")) + sorted(CSRC.glob("*.hip")) + [INCLUDE / "gpd.h"]
 ARCH = os.environ.get("GPD_OFFLOAD_ARCH", "gfx950")
+# kernarg preloading: the step kernel's leading scalar arguments arrive in SGPRs.
+# max-ilp scheduling: a step launch runs ONE wave per CU (thin blocks), so the default
+# occupancy-driven scheduler buys nothing and ILP within the wave is what hides latency.
+# (scripts/kernel_diff.py compiles the device assembly with the same list)
+DEVICE_FLAGS = [f"--offload-arch={ARCH}", "-mcode-object-version=5", "-O3", "-std=c++17",
+                "-mllvm", "-amdgpu-kernarg-preload-count=12", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 
 
 def hipcc():
@@ -41,13 +47,9 @@ def build(force=False, verbose=False, stamps=False, variant=None, defines=()):
     if not force and not stamps and not variant and not needs_build():
         return LIB_PATH
     tmp = out.with_suffix(".so.tmp")
-    # kernarg preloading: the step kernel's leading scalar arguments arrive in SGPRs.
-    # max-ilp scheduling: a step launch runs ONE wave per CU (thin blocks), so the default
-    # occupancy-driven scheduler buys nothing and ILP within the wave is what hides latency.
-    cmd = [hipcc(), f"--offload-arch={ARCH}", "-mcode-object-version=5", "-O3", "-std=c++17",
-           "-mllvm", "-amdgpu-kernarg-preload-count=12", "-mllvm", "-amdgpu-sched-strategy=max-ilp",
-           "-fPIC", "-shared", "-Wall", "-Wno-unused-result", f"-I{INCLUDE}", "-o", str(tmp),
-           str(CSRC / "gpd.hip")] + (["-DGPD_STAMPS"] if stamps else []) + [f"-D{d}" for d in defines]
+    cmd = [hipcc()] + DEVICE_FLAGS + ["-fPIC", "-shared", "-Wall", "-Wno-unused-result", f"-I{INCLUDE}", "-o", str(tmp),
+                                      str(CSRC / "gpd.hip")]
+    cmd += (["-DGPD_STAMPS"] if stamps else []) + [f"-D{d}" for d in defines]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + " ".join(cmd) + "\n" + res.stdout + res.stderr)

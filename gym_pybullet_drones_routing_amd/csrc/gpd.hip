@@ -418,11 +418,9 @@ int settle_last(gpd_sim* s, hipStream_t st) {
   if (!(s->wt & 4)) return GPD_OK;
   const SimView<R> v = make_view<R>(s);
   const Consts<R>* c = (const Consts<R>*)s->d_consts;
-  if (s->het)   // the env's own float32 hover constant
-    hipLaunchKernelGGL((last_from_ring_kernel_het<R>), dim3(grid_for(s->N, 256)), dim3(256), 0, st, v,
-                       (const R*)s->d_etab, s->epad);
-  else
-    hipLaunchKernelGGL((last_from_ring_kernel<R>), dim3(grid_for(s->N, 256)), dim3(256), 0, st, v, c);
+  // a het sim: the env's own float32 hover constant
+  const R* hover_env = s->het ? (const R*)s->d_etab + kHetHover * s->epad : nullptr;
+  hipLaunchKernelGGL((last_from_ring_kernel<R>), dim3(grid_for(s->N, 256)), dim3(256), 0, st, v, c, hover_env);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemsetAsync(s->d_ctr + s->E, 0, sizeof(int2), st));
   return GPD_OK;
@@ -632,9 +630,9 @@ template <typename R>
 int launch_reset(gpd_sim* s, const uint8_t* mask, float* obs, hipStream_t st) {
   const SimView<R> v = make_view<R>(s);
   if (s->het)   // every drone's own template
-    hipLaunchKernelGGL((reset_kernel_het<R>), dim3(grid_for(s->N, 256)), dim3(256), 0, st, v, mask, obs);
+    hipLaunchKernelGGL((reset_kernel<R, true>), dim3(grid_for(s->N, 256)), dim3(256), 0, st, v, mask, obs);
   else
-    hipLaunchKernelGGL((reset_kernel<R>), dim3(grid_for(s->N, 256)), dim3(256), 0, st, v, mask, obs);
+    hipLaunchKernelGGL((reset_kernel<R, false>), dim3(grid_for(s->N, 256)), dim3(256), 0, st, v, mask, obs);
   HIP_TRY(hipGetLastError());
   return GPD_OK;
 }

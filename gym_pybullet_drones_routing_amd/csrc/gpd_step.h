@@ -1,42 +1,10 @@
-// gpd_step.h — the one-wave step: substep_block (one physics substep of a block, with downwash
-// and the drone-contact hook), the observation tile's size and copy-out, and step_kernel
+// gpd_step.h — the one-wave step: the observation tile's size and copy-out, and step_kernel
 // (gpd_step: one env.step() per launch).  Needs the loads / stores and stamps of gpd_layout.h and
-// DcHookT (gpd_dcontact.h); the duo and wide kernels reuse what is defined here.
+// the phases of gpd_step_parts.h; the duo, wide and het kernels reuse what is defined here.
 #pragma once
-#include "gpd_dcontact.h"
+#include "gpd_step_parts.h"
 
 namespace gpd {
-
-// One physics substep of every drone of the block, including the readback that precedes it
-// (BaseAviary.py:343-372 loop body).  MULTI: envs have D > 1 drones and may need downwash.
-template <typename R, bool MULTI, int PF, bool ANGV = true>
-__device__ __forceinline__ void substep_block(Drone<R>& s, R rpm[4], R W[4], R last[4],
-                                              const Consts<R>& c, DynK<R>& k, R* sx, R* sy, R* sz, int tid,
-                                              int base, int D, DwPairs pairs, R* spair, const DcPairs& dcp) {
-  R dw = R(0);
-  if (MULTI && pf_on<PF>(k.flags, F_DW)) {
-    sx[tid] = s.px; sy[tid] = s.py; sz[tid] = s.pz;
-    wave_lds_sync();
-    if (pairs.n > 0) {
-      for (int p = tid; p < pairs.n; p += kWave) {
-        const int i = (p * pairs.dmagic) >> 20;          // drone of the block
-        const int j = p - i * D;                          // neighbour within its env
-        const int ib = ((i * pairs.dmagic) >> 20) * D;   // the env's first drone in the block
-        spair[p] = dw_pair(sx[i], sy[i], sz[i], sx[ib + j], sy[ib + j], sz[ib + j], c);
-      }
-      wave_lds_sync();
-      if (tid * D < pairs.n)
-        for (int j = 0; j < D; ++j) dw = dw + spair[tid * D + j];
-    } else {
-      dw = downwash_sum(s.px, s.py, s.pz, sx, sy, sz, base, D, c);
-    }
-    wave_lds_sync();
-  }
-  // the drone contact inlined in the compiled-in flag sets without downwash (DcHookT)
-  constexpr bool kDcInl = PF != kPfRuntime && (PF & F_DW) == 0;
-  if (MULTI) dyn_substep<R, PF, ANGV, 1, DcHookT<kDcInl>>(s, rpm, W, last, dw, c, k, DcHookT<kDcInl>{tid, dcp});
-  else dyn_substep<R, PF, ANGV>(s, rpm, W, last, dw, c, k);
-}
 
 // Bytes of dynamic LDS the step kernel needs for its observation tile: the row's columns
 // (state, history, current action).  A == 4 keeps float4 columns (state 3, history+action L);
@@ -145,6 +113,14 @@ __device__ __forceinline__ void tile_copy_out(const float4* tile4, const float* 
 // ACT: action type (GPD_ACT_*); PID types run DSLPIDControl before the substeps.
 // PF: the physics flags compiled in (pf_on): 0 = plain DYN (the bench path, aero / PYB-wrench code
 // compiled out), a flag set for the BASELINE configs' combinations, kPfRuntime for the rest.
+// The history DMA, the ring append, the terminal-row store and the reset are the helpers of
+// gpd_step_parts.h.  The action load, the peeled substep loop, the final readback, the hover
+// terms, the env reduction and the tile fill are written out here although the same header
+// defines them (step_kernel_het and step_kernel_wide call those): as calls they inline to the
+// same instructions but to another register allocation and schedule in some instantiations, and
+// this kernel's code is kept as tuned (scripts/kernel_diff.py, profiles/step_parts/).  A fix
+// to one of those phases goes to the helper AND here (and to step_kernel_duo's pose wave); the
+// peeled loop exists here and in step_kernel_het (see there).
 template <typename R, int ACT, bool MULTI, int PF, bool STREAM = false>
 // STREAM: the cache policies for batches far past the Infinity Cache (kAuxWtStream above).
 // The leading scalar arguments duplicate the SimView / StepIO fields the first loads need: the
@@ -238,20 +214,7 @@ __global__ __launch_bounds__(kWave) void step_kernel(R* __restrict__ state_p, co
   // flight, so issuing it before the state/action loads were consumed would put the DMA round
   // trip on the critical path.  Issued there it overlaps the remaining substeps.
   auto history_dma = [&]() {
-    for (int k = 0; k < nh; ++k) {
-      int slot = head + 1 + k;
-      slot -= slot >= v.ring_len ? v.ring_len : 0;
-      const float* src = v.ring + ridx(nn, slot, v.ring_len, A);
-      if (A == 4) {
-        __builtin_amdgcn_global_load_lds((gbl_void_ptr)src, (lds_void_ptr)(tile4 + (3 + k) * kPad), 16, 0,
-                                         STREAM ? kAuxDmaStream : 0);
-      } else {
-#pragma unroll
-        for (int j = 0; j < A; ++j)
-          __builtin_amdgcn_global_load_lds((gbl_void_ptr)(src + j), (lds_void_ptr)(tilef + (12 + k * A + j) * kPad), 4,
-                                           0, STREAM ? kAuxDmaStream : 0);
-      }
-    }
+    gpd::history_dma<A, STREAM ? kAuxDmaStream : 0>(v.ring, nn, head, v.ring_len, nh, tile4, tilef);
   };
   // propeller wrench: the same RPMs drive every substep of the control step (:349-367)
   R W[4];
@@ -347,13 +310,7 @@ __global__ __launch_bounds__(kWave) void step_kernel(R* __restrict__ state_p, co
   GPD_STAMP(4);
   // current action into the ring (deque.append); issued after the wait above so that the wait
   // does not also cover this store's write acknowledgement.  The DMA never reads slot `head`.
-  if (active) {
-    float* ring_cur = v.ring + ridx(n, head, v.ring_len, A);
-    if (A == 4) *reinterpret_cast<float4*>(ring_cur) = make_float4(a[0], a[1], a[2], a[3]);
-    else
-#pragma unroll
-      for (int j = 0; j < A; ++j) ring_cur[j] = a[j];
-  }
+  if (active) ring_append<A>(v.ring, n, head, v.ring_len, a);
 
 
   const int NC = A == 4 ? 3 + v.ring_len : 12 + v.ring_len * A;  // tile columns (float4 / float)
@@ -362,30 +319,8 @@ __global__ __launch_bounds__(kWave) void step_kernel(R* __restrict__ state_p, co
     // its history and action columns equal the reset row's and go out with the tile copy-out);
     // the env goes back to INIT_XYZS / INIT_RPYS (_housekeeping :458-477; SB3 DummyVecEnv keeps
     // the last obs as terminal_observation)
-    if (active && io.terminal_obs != nullptr) {
-      float* trow = io.terminal_obs + n * v.W;
-      if (A == 4) {   // W = 72: 16-byte aligned rows
-        float4* t4 = reinterpret_cast<float4*>(trow);
-        t4[0] = make_float4(row12[0], row12[1], row12[2], row12[3]);
-        t4[1] = make_float4(row12[4], row12[5], row12[6], row12[7]);
-        t4[2] = make_float4(row12[8], row12[9], row12[10], row12[11]);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 12; ++k) trow[k] = row12[k];
-      }
-    }
-    const R* ini = MULTI ? v.init + d * 10 : c.init0;
-    s.px = ini[0]; s.py = ini[1]; s.pz = ini[2];
-    s.qx = ini[3]; s.qy = ini[4]; s.qz = ini[5]; s.qw = ini[6];
-    s.vx = s.vy = s.vz = R(0);
-    s.wx = s.wy = s.wz = R(0);
-    s.ax = s.ay = s.az = R(0);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) last[k] = R(0);
-    row12[0] = (float)ini[0]; row12[1] = (float)ini[1]; row12[2] = (float)ini[2];
-    row12[3] = (float)ini[7]; row12[4] = (float)ini[8]; row12[5] = (float)ini[9];
-#pragma unroll
-    for (int k = 6; k < 12; ++k) row12[k] = 0.0f;
+    if (active && io.terminal_obs != nullptr) row12_store<A>(io.terminal_obs + n * v.W, row12);
+    reset_to_template(MULTI ? v.init + d * 10 : c.init0, s, last, row12);
   }
   // bit r set <=> tile row r belongs to an env that finished this step (tile rows are lanes)
   const unsigned long long done_rows = __ballot(do_reset && active && io.terminal_obs != nullptr);

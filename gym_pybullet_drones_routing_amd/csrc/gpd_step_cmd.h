@@ -8,7 +8,7 @@
 // then PYB_STEPS_PER_CTRL substeps on those RPMs (BaseAviary.py:343-372), the final readback and
 // the 20-float state vectors (_getDroneStateVector :541-561) as the observation.  No reward, no
 // done flag, no auto-reset, and the action ring of the RL step is left alone.
-// Needs substep_block (gpd_step.h) and wide_downwash (gpd_step_wide.h).
+// Needs substeps_cmd, state20_row and load_rpm4 (gpd_step_parts.h) and wide_downwash (gpd_step_wide.h).
 #pragma once
 #include "gpd_step_wide.h"
 
@@ -16,60 +16,94 @@ namespace gpd {
 
 enum : int { CMD_RPM = 0, CMD_VEL = 1, CMD_WAYPOINT = 2 };
 
-// The command of one drone -> its four RPMs.  CTRL: the controller modes (VEL / WAYPOINT; cs is the
-// drone's controller state, updated in place), else RPM.  `mode` is wave-uniform.
-// actions: RPM real [N][4] (the sim's precision: float64 controller outputs lose nothing),
-// VEL float [N][4], WAYPOINT real [N][7] = target_pos(3) target_yaw target_vel(3).
+// The command of one drone -> its four RPMs, in two halves so that the rollout (gpd_step_rollout.h)
+// can load a step's row while the step before it integrates.  CTRL: the controller modes (VEL /
+// WAYPOINT), else RPM; `mode` is wave-uniform.
+// actions: RPM real [..][N][4] (the sim's precision: float64 controller outputs lose nothing),
+// VEL float [..][N][4], WAYPOINT real [..][N][7] = target_pos(3) target_yaw target_vel(3).
+// Register width of a command row: RPM 4 reals, VEL 4 floats (held as reals: exact), WAYPOINT 7 reals.
+template <bool CTRL>
+constexpr int cmd_row_regs() { return CTRL ? 7 : 4; }
+
+// Command row `row` (= step * N + drone) into registers.  RPM and VEL rows are one aligned vector
+// (host-checked base pointer); a waypoint row is 7 reals, not 16-byte aligned for odd drones:
+// scalar loads.
+template <typename R, bool CTRL>
+__device__ __forceinline__ void cmd_row_load(const void* __restrict__ actions, int mode, long long row,
+                                             R a[cmd_row_regs<CTRL>()]) {
+  if (!CTRL) {
+    load_rpm4((const R*)actions + row * 4, a);
+  } else if (mode == CMD_VEL) {
+    float q[4];
+    load_rpm4((const float*)actions + row * 4, q);
+    a[0] = (R)q[0]; a[1] = (R)q[1]; a[2] = (R)q[2]; a[3] = (R)q[3];
+    a[4] = a[5] = a[6] = R(0);
+  } else {
+    const R* w = (const R*)actions + row * 7;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) a[k] = w[k];
+  }
+}
+
+// The controller modes: DSLPIDControl.computeControl on the state of the last readback; cs is the
+// drone's controller state, updated in place.  targets(pos, rpy, tpos, tyaw, tvel) fills in the
+// command's targets: from the row in registers (cmd_row_to_rpm) or straight from memory
+// (cmd_to_rpm; a single step has no row to prefetch, and holding the 7 reals across the mode
+// branch spills in the f64 kernels).
+template <typename R, typename F>
+__device__ __forceinline__ void cmd_ctrl_rpm(const Consts<R>& c, const Drone<R>& s, R cs[9], R rpm[4], F&& targets) {
+  R qn[4], Rm[9], rpy[3];
+  readback_fused(s.qx, s.qy, s.qz, s.qw, qn, Rm);
+  quat_to_euler(qn, rpy[0], rpy[1], rpy[2]);
+  const R pos[3] = {s.px, s.py, s.pz}, vel[3] = {s.vx, s.vy, s.vz};
+  R tpos[3], tvel[3], tyaw;
+  targets(pos, rpy, tpos, tyaw, tvel);
+  dsl_pid<R, false>(c.pid, pos, Rm, rpy, vel, tpos, tyaw, tvel, cs, rpm);
+}
+
+// The row in registers -> RPMs.
+template <typename R, bool CTRL>
+__device__ __forceinline__ void cmd_row_to_rpm(const Consts<R>& c, int mode, const R a[cmd_row_regs<CTRL>()], R max_rpm,
+                                               const Drone<R>& s, R cs[9], R rpm[4]) {
+  if (!CTRL) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) rpm[k] = np_clip(a[k], R(0), max_rpm);
+  } else {
+    cmd_ctrl_rpm(c, s, cs, rpm, [&](const R pos[3], const R rpy[3], R tpos[3], R& tyaw, R tvel[3]) {
+      if (mode == CMD_VEL) {
+        const float af[4] = {(float)a[0], (float)a[1], (float)a[2], (float)a[3]};
+        pid_targets<R, ACT_VEL>(c.pid, af, pos, rpy, tpos, tyaw, tvel);
+      } else {
+        tpos[0] = a[0]; tpos[1] = a[1]; tpos[2] = a[2];
+        tyaw = a[3];
+        tvel[0] = a[4]; tvel[1] = a[5]; tvel[2] = a[6];
+      }
+    });
+  }
+}
+
+// Drone n's command of a single step -> RPMs.
 template <typename R, bool CTRL>
 __device__ __forceinline__ void cmd_to_rpm(const Consts<R>& c, int mode, const void* __restrict__ actions, long long n,
                                            R max_rpm, const Drone<R>& s, R cs[9], R rpm[4]) {
   if (!CTRL) {
-    const R* src = (const R*)actions + n * 4;
-    typedef double gpd_d2 __attribute__((ext_vector_type(2)));
-    typedef float gpd_f4 __attribute__((ext_vector_type(4)));
     R a[4];
-    if (sizeof(R) == 8) {   // a drone's row is one aligned 32-byte run (host-checked)
-      const gpd_d2 lo = reinterpret_cast<const gpd_d2*>(src)[0], hi = reinterpret_cast<const gpd_d2*>(src)[1];
-      a[0] = (R)lo.x; a[1] = (R)lo.y; a[2] = (R)hi.x; a[3] = (R)hi.y;
-    } else {
-      const gpd_f4 q = *reinterpret_cast<const gpd_f4*>(src);
-      a[0] = (R)q.x; a[1] = (R)q.y; a[2] = (R)q.z; a[3] = (R)q.w;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) rpm[k] = np_clip(a[k], R(0), max_rpm);
+    cmd_row_load<R, false>(actions, mode, n, a);
+    cmd_row_to_rpm<R, false>(c, mode, a, max_rpm, s, cs, rpm);
   } else {
-    R qn[4], Rm[9], rpy[3];
-    readback_fused(s.qx, s.qy, s.qz, s.qw, qn, Rm);
-    quat_to_euler(qn, rpy[0], rpy[1], rpy[2]);
-    const R pos[3] = {s.px, s.py, s.pz}, vel[3] = {s.vx, s.vy, s.vz};
-    R tpos[3], tvel[3], tyaw;
-    if (mode == CMD_VEL) {
-      const float4 q = *reinterpret_cast<const float4*>((const float*)actions + n * 4);
-      const float a[4] = {q.x, q.y, q.z, q.w};
-      pid_targets<R, ACT_VEL>(c.pid, a, pos, rpy, tpos, tyaw, tvel);
-    } else {
-      const R* w = (const R*)actions + n * 7;
-      tpos[0] = w[0]; tpos[1] = w[1]; tpos[2] = w[2];
-      tyaw = w[3];
-      tvel[0] = w[4]; tvel[1] = w[5]; tvel[2] = w[6];
-    }
-    dsl_pid<R, false>(c.pid, pos, Rm, rpy, vel, tpos, tyaw, tvel, cs, rpm);
+    cmd_ctrl_rpm(c, s, cs, rpm, [&](const R pos[3], const R rpy[3], R tpos[3], R& tyaw, R tvel[3]) {
+      if (mode == CMD_VEL) {
+        float a[4];
+        load_rpm4((const float*)actions + n * 4, a);
+        pid_targets<R, ACT_VEL>(c.pid, a, pos, rpy, tpos, tyaw, tvel);
+      } else {
+        const R* w = (const R*)actions + n * 7;
+        tpos[0] = w[0]; tpos[1] = w[1]; tpos[2] = w[2];
+        tyaw = w[3];
+        tvel[0] = w[4]; tvel[1] = w[5]; tvel[2] = w[6];
+      }
+    });
   }
-}
-
-// The 20-float state vector of a drone after the step's last readback (the literal Bullet
-// readback of state20_kernel: exact gimbal branches).
-template <typename R>
-__device__ __forceinline__ void state20_row(const Drone<R>& s, const R last[4], R o[20]) {
-  R qn[4], roll, pitch, yaw;
-  quat_readback(s.qx, s.qy, s.qz, s.qw, qn);
-  quat_to_euler(qn, roll, pitch, yaw);
-  o[0] = s.px; o[1] = s.py; o[2] = s.pz;
-  o[3] = qn[0]; o[4] = qn[1]; o[5] = qn[2]; o[6] = qn[3];
-  o[7] = roll; o[8] = pitch; o[9] = yaw;
-  o[10] = s.vx; o[11] = s.vy; o[12] = s.vz;
-  o[13] = s.ax; o[14] = s.ay; o[15] = s.az;
-  o[16] = last[0]; o[17] = last[1]; o[18] = last[2]; o[19] = last[3];
 }
 
 // Copy-out of a one-wave block's state20 rows: the rows are [nact][20] reals, contiguous in HBM
@@ -93,6 +127,18 @@ __device__ __forceinline__ void rows20_copy_out(const R* tile, int lane, int nac
     for (int g = 0; g < G; ++g) q[g] = tile[(col + g) * kPad + row];
     reinterpret_cast<gpd_vec*>(dst)[i] = q;
   }
+}
+
+// The block's state20 rows (state20_row of every lane) through the LDS tile `rows` to dst.
+template <typename R>
+__device__ __forceinline__ void rows20_stage_out(R* rows, int tid, int nact, const Drone<R>& s, const R last[4],
+                                                 R* __restrict__ dst) {
+  R o[20];
+  state20_row(s, last, o);
+#pragma unroll
+  for (int k = 0; k < 20; ++k) rows[k * kPad + tid] = o[k];
+  wave_lds_sync();
+  rows20_copy_out(rows, tid, nact, dst);
 }
 
 // The command step stores last_clipped_action into the state itself, so it takes back the mark an
@@ -138,31 +184,11 @@ __global__ __launch_bounds__(kWave) void cmd_step_kernel(SimView<R> v, const Con
     for (int k = 0; k < 9; ++k) cs[k] = v.ctrl[tidx(nn, k, 9)];
   }
   cmd_to_rpm<R, CTRL>(c, mode, actions, nn, max_rpm, s, cs, rpm);
-  // the same RPMs and wrench drive every substep; the drag of substep 1 sees the previous step's
-  // RPMs (BaseAviary.py:359-372)
+  // the same RPMs and wrench drive every substep
   R W[4];
   rpm_wrench<R, PF>(rpm, dk, c, W);
-  if (PF == 0) {   // the write-only world ang_v from the last substep only
-    for (int it = 0; it < dk.nsub - 1; ++it)
-      substep_block<R, MULTI, PF, false>(s, rpm, W, last, c, dk, sx, sy, sz, tid, base, D, DwPairs{0, 0}, nullptr, dcp);
-    substep_block<R, MULTI, PF, true>(s, rpm, W, last, c, dk, sx, sy, sz, tid, base, D, DwPairs{0, 0}, nullptr, dcp);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) last[k] = rpm[k];
-  } else {         // one copy of the substep (its plane and pair solves are most of the kernel's code)
-    for (int it = 0; it < dk.nsub; ++it) {
-      substep_block<R, MULTI, PF, true>(s, rpm, W, last, c, dk, sx, sy, sz, tid, base, D, DwPairs{0, 0}, nullptr, dcp);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) last[k] = rpm[k];   // self.last_clipped_action = clipped_action  :372
-    }
-  }
-  if (obs20) {
-    R o[20];
-    state20_row(s, last, o);
-#pragma unroll
-    for (int k = 0; k < 20; ++k) rows[k * kPad + tid] = o[k];
-    wave_lds_sync();
-    rows20_copy_out(rows, tid, nact, obs20 + n0 * 20);
-  }
+  substeps_cmd<R, MULTI, PF>(s, rpm, W, last, c, dk, sx, sy, sz, tid, base, D, dcp);
+  if (obs20) rows20_stage_out(rows, tid, nact, s, last, obs20 + n0 * 20);
   if (!active) return;
   store_drone(v, n, s, last);
   unmark_last_in_ring(v, n);
@@ -210,13 +236,7 @@ __global__ __launch_bounds__(MAXT) void cmd_step_kernel_wide(SimView<R> v, const
     for (int k = 0; k < 4; ++k) last[k] = rpm[k];
   }
   if (!active) return;
-  if (obs20) {
-    R o[20];
-    state20_row(s, last, o);
-    R* dst = obs20 + n * 20;
-#pragma unroll
-    for (int k = 0; k < 20; ++k) dst[k] = o[k];
-  }
+  if (obs20) state20_store(s, last, obs20 + n * 20);
   store_drone(v, n, s, last);
   unmark_last_in_ring(v, n);
   if (CTRL) {

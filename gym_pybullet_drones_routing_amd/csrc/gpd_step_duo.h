@@ -26,6 +26,9 @@ namespace gpd {
 // the current action) WHILE the pose / rate waves integrate, and appends the action to the
 // ring.  The pose wave then stores only the 12 state columns of its rows straight from
 // registers, so the LDS observation tile and its copy-out leave the critical path.
+// Of the phases of gpd_step_parts.h the ring append, the terminal-row store and the reset are
+// calls; the action load, the final readback and the tile fill stay written out, for the reason
+// given at step_kernel (gpd_step.h).  The history DMAs and the hover terms are this kernel's own.
 template <typename R, int ACT, bool IO>
 __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R* __restrict__ state_p,
                                                              const float* __restrict__ actions_p,
@@ -83,11 +86,7 @@ __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R*
     // an LDS-DMA in flight makes the compiler wait for the whole DMA (vmcnt(0)) first.
     if (A == 4) tile4[(L - 1) * kPad + tid] = make_float4(a[0], a[1], a[2], a[3]);
     else tilef[(L - 1) * kPad + tid] = a[0];
-    if (active) {      // deque.append of the current action; the DMA never reads slot `head`
-      float* ring_cur = v.ring + ridx(n, hd, L, A);
-      if (A == 4) *reinterpret_cast<float4*>(ring_cur) = make_float4(a[0], a[1], a[2], a[3]);
-      else ring_cur[0] = a[0];
-    }
+    if (active) ring_append<A>(v.ring, n, hd, L, a);   // deque.append; the DMA never reads slot `head`
     // Everything the tail needs that does not depend on the DMA'd data is formed in the slack
     // the wave has at the hand-off barriers (its tail is the end of the block's critical path)
     // and pinned in registers across them:
@@ -327,13 +326,8 @@ __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R*
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // history DMA has landed in the tile
-    if (active) {      // current action into the ring (deque.append); the DMA never reads `head`
-      float* ring_cur = v.ring + ridx(n, head, v.ring_len, A);
-      if (A == 4) *reinterpret_cast<float4*>(ring_cur) = make_float4(a[0], a[1], a[2], a[3]);
-      else
-#pragma unroll
-        for (int j = 0; j < A; ++j) ring_cur[j] = a[j];
-    }
+    // current action into the ring (deque.append); the DMA never reads `head`
+    if (active) ring_append<A>(v.ring, n, head, v.ring_len, a);
     if (A == 4) {
       tile4[(3 + nh) * kPad + tid] = make_float4(a[0], a[1], a[2], a[3]);
     } else {
@@ -451,30 +445,8 @@ __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R*
   float row12[12] = {(float)s.px, (float)s.py, (float)s.pz, roll, pitch, yaw,
                      (float)s.vx, (float)s.vy, (float)s.vz, (float)s.ax, (float)s.ay, (float)s.az};
   if (do_reset) {
-    if (active && io.terminal_obs != nullptr) {
-      float* trow = io.terminal_obs + n * v.W;
-      if (A == 4) {
-        float4* t4 = reinterpret_cast<float4*>(trow);
-        t4[0] = make_float4(row12[0], row12[1], row12[2], row12[3]);
-        t4[1] = make_float4(row12[4], row12[5], row12[6], row12[7]);
-        t4[2] = make_float4(row12[8], row12[9], row12[10], row12[11]);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 12; ++k) trow[k] = row12[k];
-      }
-    }
-    const R* ini = tk.ini;
-    s.px = ini[0]; s.py = ini[1]; s.pz = ini[2];
-    s.qx = ini[3]; s.qy = ini[4]; s.qz = ini[5]; s.qw = ini[6];
-    s.vx = s.vy = s.vz = R(0);
-    s.wx = s.wy = s.wz = R(0);
-    s.ax = s.ay = s.az = R(0);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) last[k] = R(0);
-    row12[0] = (float)ini[0]; row12[1] = (float)ini[1]; row12[2] = (float)ini[2];
-    row12[3] = (float)ini[7]; row12[4] = (float)ini[8]; row12[5] = (float)ini[9];
-#pragma unroll
-    for (int k = 6; k < 12; ++k) row12[k] = 0.0f;
+    if (active && io.terminal_obs != nullptr) row12_store<A>(io.terminal_obs + n * v.W, row12);
+    reset_to_template(tk.ini, s, last, row12);
   }
   const unsigned long long done_rows = __ballot(do_reset && active && io.terminal_obs != nullptr);
   // what the last stores write, formed before the final barrier (the stores stay behind it)

@@ -4,70 +4,17 @@
 // state goes through HBM once per launch instead of once per step, and the state20 rows are
 // stored only on the steps the caller records.  The commands of the flight are a
 // [n_steps][N][w] tensor; the next step's row is loaded while the current step's substeps run.
-// The per-step arithmetic is cmd_step_kernel's, operation for operation (cmd_row_to_rpm is
-// cmd_to_rpm on a row already in registers).
+// The per-step arithmetic is cmd_step_kernel's: the same clip / cmd_ctrl_rpm (here on a row
+// already in registers, cmd_row_to_rpm).  The substep loop and the staging of the state20 rows are
+// written out here although substeps_cmd (gpd_step_parts.h) and rows20_stage_out (gpd_step_cmd.h)
+// define them for cmd_step_kernel: as calls they change this kernel's schedule, and the
+// single-drone RPM rollout measured 1.4 % slower (profiles/step_parts/).  A fix to either goes to
+// the helper AND here.
 // Needs cmd_step_kernel's helpers (gpd_step_cmd.h).
 #pragma once
 #include "gpd_step_cmd.h"
 
 namespace gpd {
-
-// Register width of a command row: RPM 4 reals, VEL 4 floats (held as reals: exact), WAYPOINT 7 reals.
-template <bool CTRL>
-constexpr int cmd_row_regs() { return CTRL ? 7 : 4; }
-
-// Command row `row` (= step * N + drone) of the flight into registers.  RPM and VEL rows are one
-// aligned vector (host-checked base pointer, as gpd_cmd_step's); a waypoint row is 7 reals, not
-// 16-byte aligned for odd drones: scalar loads.
-template <typename R, bool CTRL>
-__device__ __forceinline__ void cmd_row_load(const void* __restrict__ actions, int mode, long long row,
-                                             R a[cmd_row_regs<CTRL>()]) {
-  typedef double gpd_d2 __attribute__((ext_vector_type(2)));
-  typedef float gpd_f4 __attribute__((ext_vector_type(4)));
-  if (!CTRL) {
-    const R* src = (const R*)actions + row * 4;
-    if (sizeof(R) == 8) {
-      const gpd_d2 lo = reinterpret_cast<const gpd_d2*>(src)[0], hi = reinterpret_cast<const gpd_d2*>(src)[1];
-      a[0] = (R)lo.x; a[1] = (R)lo.y; a[2] = (R)hi.x; a[3] = (R)hi.y;
-    } else {
-      const gpd_f4 q = *reinterpret_cast<const gpd_f4*>(src);
-      a[0] = (R)q.x; a[1] = (R)q.y; a[2] = (R)q.z; a[3] = (R)q.w;
-    }
-  } else if (mode == CMD_VEL) {
-    const gpd_f4 q = *reinterpret_cast<const gpd_f4*>((const float*)actions + row * 4);
-    a[0] = (R)q.x; a[1] = (R)q.y; a[2] = (R)q.z; a[3] = (R)q.w;
-    a[4] = a[5] = a[6] = R(0);
-  } else {
-    const R* w = (const R*)actions + row * 7;
-#pragma unroll
-    for (int k = 0; k < 7; ++k) a[k] = w[k];
-  }
-}
-
-// cmd_to_rpm (gpd_step_cmd.h) on a row in registers: the same operations in the same order.
-template <typename R, bool CTRL>
-__device__ __forceinline__ void cmd_row_to_rpm(const Consts<R>& c, int mode, const R a[cmd_row_regs<CTRL>()], R max_rpm,
-                                               const Drone<R>& s, R cs[9], R rpm[4]) {
-  if (!CTRL) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) rpm[k] = np_clip(a[k], R(0), max_rpm);
-  } else {
-    R qn[4], Rm[9], rpy[3];
-    readback_fused(s.qx, s.qy, s.qz, s.qw, qn, Rm);
-    quat_to_euler(qn, rpy[0], rpy[1], rpy[2]);
-    const R pos[3] = {s.px, s.py, s.pz}, vel[3] = {s.vx, s.vy, s.vz};
-    R tpos[3], tvel[3], tyaw;
-    if (mode == CMD_VEL) {
-      const float af[4] = {(float)a[0], (float)a[1], (float)a[2], (float)a[3]};
-      pid_targets<R, ACT_VEL>(c.pid, af, pos, rpy, tpos, tyaw, tvel);
-    } else {
-      tpos[0] = a[0]; tpos[1] = a[1]; tpos[2] = a[2];
-      tyaw = a[3];
-      tvel[0] = a[4]; tvel[1] = a[5]; tvel[2] = a[6];
-    }
-    dsl_pid<R, false>(c.pid, pos, Rm, rpy, vel, tpos, tyaw, tvel, cs, rpm);
-  }
-}
 
 // One step's tracking figures: |pos - target|^2 added to the sum, its root folded into the max.
 // Every product and sum rounded (np.linalg.norm's operations, as adjacency_kernel).

@@ -1,7 +1,8 @@
 // gpd_step_wide.h — the remaining kernels: step_kernel_wide / integrate_kernel_wide (envs of more
 // than 64 drones, or rows that overflow the one-wave tile), integrate_kernel (gpd_integrate: raw
 // substeps with explicit RPMs) and the utility kernels (reset, state export / import, layout
-// conversion).  Needs gpd_layout.h, DcHookT (gpd_dcontact.h) and substep_block (gpd_step.h).
+// conversion).  Needs gpd_layout.h, DcHookT (gpd_dcontact.h) and the phases of gpd_step_parts.h
+// (substep_block, action_load, obs_angles, hover_terms, reset_to_template, state20_store, load_rpm4).
 #pragma once
 #include "gpd_step_duo.h"
 
@@ -121,8 +122,7 @@ __global__ __launch_bounds__(MAXT) void step_kernel_wide(SimView<R> v, StepIO<R>
   const int2 cv = v.ctr[es];
   const int sc = cv.x, head = cv.y;
   float a[A];
-#pragma unroll
-  for (int j = 0; j < A; ++j) a[j] = io.actions[n * A + j];
+  action_load<A>(io.actions, n, a);
   DynK<R> dk = dyn_consts(c);
   R rpm[4];
   R cs[9];
@@ -152,23 +152,14 @@ __global__ __launch_bounds__(MAXT) void step_kernel_wide(SimView<R> v, StepIO<R>
     for (int k = 0; k < 4; ++k) last[k] = rpm[k];   // self.last_clipped_action = clipped_action  :372
   }
   // final readback (:374) -> obs / reward / done
-  R qn[4], Rm[9];
-  readback_fused(s.qx, s.qy, s.qz, s.qw, qn, Rm);
-  AttitudeArgs<R> att = attitude_args(qn);
-  bool tilted, up_unused;   // |roll| or |pitch| > 0.4, decided exactly near the limit (attitude_decide)
-  attitude_decide<R, true, false>(s.qx, s.qy, s.qz, s.qw, att, tilted, up_unused);
   float roll, pitch, yaw;
-  obs_euler_f32(qn, att, roll, pitch, yaw);
+  const bool tilted = obs_angles(s, roll, pitch, yaw);
   float reward = -1.0f;
   bool term = false, trunc = false;
   if (v.task != TASK_NONE) {
-    const R* tg = v.target + (active ? d : 0) * 3;
-    const R tx = tg[0] - s.px, ty = tg[1] - s.py, tz = tg[2] - s.pz;
-    const R d2 = tx * tx + ty * ty + tz * tz;
-    const R dist = g_sqrt(d2);
-    R r = R(2) - d2 * d2;
-    r = r > R(0) ? r : R(0);
-    const bool oob = g_abs(s.px) > v.bound_xy || g_abs(s.py) > v.bound_xy || s.pz > R(2) || tilted;
+    R r, dist;
+    bool oob;
+    hover_terms(v.target + (active ? d : 0) * 3, s, v.bound_xy, tilted, r, dist, oob);
     __syncthreads();
     if (active) { sx[t] = r; sy[t] = dist; sflag[t] = oob ? 1 : 0; }
     __syncthreads();
@@ -207,22 +198,14 @@ __global__ __launch_bounds__(MAXT) void step_kernel_wide(SimView<R> v, StepIO<R>
     orow[12 + (L - 1) * A + j] = a[j];
     if (trow) trow[12 + (L - 1) * A + j] = a[j];
   }
-  float* ring_cur = v.ring + ridx(n, head, L, A);     // deque.append (slot head is not read above)
+  // deque.append (slot head is not read above); float by float: ring_append's 16-byte store costs
+  // step_kernel_wide<double, ACT_VEL, 256> two more registers
+  float* ring_cur = v.ring + ridx(n, head, L, A);
   for (int j = 0; j < A; ++j) ring_cur[j] = a[j];
   if (do_reset) {
     if (trow)
       for (int k = 0; k < 12; ++k) trow[k] = row12[k];
-    const R* ini = v.init + d * 10;
-    s.px = ini[0]; s.py = ini[1]; s.pz = ini[2];
-    s.qx = ini[3]; s.qy = ini[4]; s.qz = ini[5]; s.qw = ini[6];
-    s.vx = s.vy = s.vz = R(0);
-    s.wx = s.wy = s.wz = R(0);
-    s.ax = s.ay = s.az = R(0);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) last[k] = R(0);
-    row12[0] = (float)ini[0]; row12[1] = (float)ini[1]; row12[2] = (float)ini[2];
-    row12[3] = (float)ini[7]; row12[4] = (float)ini[8]; row12[5] = (float)ini[9];
-    for (int k = 6; k < 12; ++k) row12[k] = 0.0f;
+    reset_to_template(v.init + d * 10, s, last, row12);
   }
   for (int k = 0; k < 12; ++k) orow[k] = row12[k];
   store_drone_step(v, n, s, last);
@@ -266,18 +249,7 @@ __global__ __launch_bounds__(MAXT) void integrate_kernel_wide(SimView<R> v, cons
     else dyn_substep<R, kPfRuntime, true, 1>(s, rpm, W, last, dw, c, dk);
 #pragma unroll
     for (int k = 0; k < 4; ++k) last[k] = rpm[k];
-    if (TRAJ && active) {
-      R qn[4], roll, pitch, yaw;   // the literal Bullet readback (as state20): exact gimbal branches
-      quat_readback(s.qx, s.qy, s.qz, s.qw, qn);
-      quat_to_euler(qn, roll, pitch, yaw);
-      R* o = traj + ((long long)t * N + n) * 20;
-      o[0] = s.px; o[1] = s.py; o[2] = s.pz;
-      o[3] = qn[0]; o[4] = qn[1]; o[5] = qn[2]; o[6] = qn[3];
-      o[7] = roll; o[8] = pitch; o[9] = yaw;
-      o[10] = s.vx; o[11] = s.vy; o[12] = s.vz;
-      o[13] = s.ax; o[14] = s.ay; o[15] = s.az;
-      o[16] = last[0]; o[17] = last[1]; o[18] = last[2]; o[19] = last[3];
-    }
+    if (TRAJ && active) state20_store(s, last, traj + ((long long)t * N + n) * 20);
   }
   if (active && n_sub > 0) store_drone(v, n, s, last);
 }
@@ -300,7 +272,6 @@ __global__ __launch_bounds__(kWave) void integrate_kernel(SimView<R> v, const Co
   const long long n = (long long)blockIdx.x * v.tpb + tid;
   const bool active = tid < v.tpb && n < v.N;
   const long long nn = active ? n : (long long)blockIdx.x * v.tpb;   // the block's first drone (step_kernel)
-  (void)d;
   const long long nleft = v.N - (long long)blockIdx.x * v.tpb;
   const int nact = (int)(nleft < v.tpb ? nleft : v.tpb);
   Drone<R> s;
@@ -310,30 +281,8 @@ __global__ __launch_bounds__(kWave) void integrate_kernel(SimView<R> v, const Co
   DynK<R> dk = dyn_consts(c);
   const DcPairs dcp = dc_enabled<MULTI, PF>(c.flags) ? dc_pairs_for(v, tid, nact) : dc_pairs_none();
   // RPMs are loaded two substeps ahead of their use (substeps t+1 and t+2 in flight while t
-  // integrates): more bytes in flight per wave for the HBM stream.  A drone's 4 RPMs are one
-  // aligned 4*sizeof(R)-byte vector (rows of the [T][N][4] tensor).
-  using V = typename std::conditional<sizeof(R) == 8, double2, float4>::type;
-  auto load4 = [&](int t, R out[4]) {
-    const R* src = rpm_in + ((long long)t * N + nn) * 4;
-    typedef double gpd_d2 __attribute__((ext_vector_type(2)));
-    typedef float gpd_f4 __attribute__((ext_vector_type(4)));
-    if (sizeof(R) == 8) {
-      gpd_d2 a, b;
-      if (STREAM) {
-        a = __builtin_nontemporal_load(reinterpret_cast<const gpd_d2*>(src));
-        b = __builtin_nontemporal_load(reinterpret_cast<const gpd_d2*>(src) + 1);
-      } else {
-        a = reinterpret_cast<const gpd_d2*>(src)[0];
-        b = reinterpret_cast<const gpd_d2*>(src)[1];
-      }
-      out[0] = (R)a.x; out[1] = (R)a.y; out[2] = (R)b.x; out[3] = (R)b.y;
-    } else {
-      const gpd_f4 a = STREAM ? __builtin_nontemporal_load(reinterpret_cast<const gpd_f4*>(src))
-                              : *reinterpret_cast<const gpd_f4*>(src);
-      out[0] = (R)a.x; out[1] = (R)a.y; out[2] = (R)a.z; out[3] = (R)a.w;
-    }
-  };
-  (void)sizeof(V);
+  // integrates): more bytes in flight per wave for the HBM stream.
+  auto load4 = [&](int t, R out[4]) { load_rpm4<R, STREAM>(rpm_in + ((long long)t * N + nn) * 4, out); };
   R nxt[4], nxt2[4];
   if (n_sub > 0) load4(0, nxt);
   if (n_sub > 1) load4(1, nxt2);
@@ -347,18 +296,8 @@ __global__ __launch_bounds__(kWave) void integrate_kernel(SimView<R> v, const Co
     substep_block<R, MULTI, PF>(s, rpm, W, last, c, dk, sx, sy, sz, tid, base, D, DwPairs{0, 0}, nullptr, dcp);
 #pragma unroll
     for (int k = 0; k < 4; ++k) last[k] = rpm[k];
-    if (TRAJ && active) {   // TRAJ: the trajectory variant (its readback / Euler registers stay out of the other)
-      R qn[4], roll, pitch, yaw;   // the literal Bullet readback (as state20): exact gimbal branches
-      quat_readback(s.qx, s.qy, s.qz, s.qw, qn);
-      quat_to_euler(qn, roll, pitch, yaw);
-      R* o = traj + ((long long)t * N + n) * 20;
-      o[0] = s.px; o[1] = s.py; o[2] = s.pz;
-      o[3] = qn[0]; o[4] = qn[1]; o[5] = qn[2]; o[6] = qn[3];
-      o[7] = roll; o[8] = pitch; o[9] = yaw;
-      o[10] = s.vx; o[11] = s.vy; o[12] = s.vz;
-      o[13] = s.ax; o[14] = s.ay; o[15] = s.az;
-      o[16] = last[0]; o[17] = last[1]; o[18] = last[2]; o[19] = last[3];
-    }
+    // TRAJ: the trajectory variant (its readback / Euler registers stay out of the other)
+    if (TRAJ && active) state20_store(s, last, traj + ((long long)t * N + n) * 20);
   }
   if (!active) return;
   if (n_sub == 0) return;
@@ -366,30 +305,25 @@ __global__ __launch_bounds__(kWave) void integrate_kernel(SimView<R> v, const Co
 }
 
 // ---------------------------------------------------------------------------------------
-// gpd_reset: masked re-initialisation (+ reset observation rows).
-template <typename R>
+// gpd_reset: masked re-initialisation (+ reset observation rows).  HET: v.init holds a template
+// per drone of every env ([E][D][10], gpd_step_het.h), else one per drone of an env ([D][10]).
+template <typename R, bool HET>
 __global__ __launch_bounds__(256) void reset_kernel(SimView<R> v, const uint8_t* __restrict__ mask, float* obs) {
   const long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= v.N) return;
   const long long e = n / v.D;
   const int d = (int)(n - e * v.D);
   if (mask && mask[e] == 0) return;
-  const R* ini = v.init + d * 10;
+  const R* ini = v.init + (HET ? n : d) * 10;
   Drone<R> s;
-  s.px = ini[0]; s.py = ini[1]; s.pz = ini[2];
-  s.qx = ini[3]; s.qy = ini[4]; s.qz = ini[5]; s.qw = ini[6];
-  s.vx = s.vy = s.vz = R(0);
-  s.wx = s.wy = s.wz = R(0);
-  s.ax = s.ay = s.az = R(0);
+  drone_from_template(ini, s);
   R last[4] = {R(0), R(0), R(0), R(0)};
   store_drone(v, n, s, last);
   const int head = v.ctr[e].y;
   if (d == 0) v.ctr[e].x = 0;
   if (obs) {
     float* orow = obs + n * v.W;
-    orow[0] = (float)ini[0]; orow[1] = (float)ini[1]; orow[2] = (float)ini[2];
-    orow[3] = (float)ini[7]; orow[4] = (float)ini[8]; orow[5] = (float)ini[9];
-    for (int k = 6; k < 12; ++k) orow[k] = 0.0f;
+    row12_from_template(ini, orow);
     const int A = v.A;
     for (int k = 0; k < v.ring_len; ++k) {   // oldest first: the slot about to be overwritten
       int slot = head + k;
@@ -404,18 +338,21 @@ __global__ __launch_bounds__(256) void reset_kernel(SimView<R> v, const uint8_t*
 // state[16..19] = action_to_rpm of its ring's newest slot (head - 1 after the step; the same
 // float32 mapping as the step, _preprocessAction BaseRLAviary.py:191-192), or 0 when its env's
 // step_counter is 0 (_housekeeping zeroes last_clipped_action, BaseAviary.py:466).  The caller
-// clears the mark afterwards (stream order).
+// clears the mark afterwards (stream order).  hover_env: a het sim's per-env column of
+// float32(HOVER_RPM) values (etab's kHetHover, gpd_step_het.h), null for the sim-wide constant.
 template <typename R>
-__global__ __launch_bounds__(256) void last_from_ring_kernel(SimView<R> v, const Consts<R>* __restrict__ c) {
+__global__ __launch_bounds__(256) void last_from_ring_kernel(SimView<R> v, const Consts<R>* __restrict__ c,
+                                                             const R* __restrict__ hover_env) {
   const long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= v.N) return;
   if (v.ctr[v.N / v.D].x == 0) return;
-  const int2 cv = v.ctr[n / v.D];
+  const long long e = n / v.D;
+  const int2 cv = v.ctr[e];
   R last[4] = {R(0), R(0), R(0), R(0)};
   if (cv.x != 0) {
     const int slot = cv.y == 0 ? v.ring_len - 1 : cv.y - 1;
     const float* a = v.ring + ridx(n, slot, v.ring_len, v.A);
-    const float hover = c->hover_f32;
+    const float hover = hover_env ? (float)hover_env[e] : c->hover_f32;
     for (int k = 0; k < 4; ++k) last[k] = (R)action_to_rpm(hover, a[v.A == 4 ? k : 0]);
   }
   for (int k = 0; k < 4; ++k) v.state[tidx(n, 16 + k, kStateComps)] = last[k];
@@ -434,15 +371,7 @@ __global__ __launch_bounds__(256) void state20_kernel(SimView<R> v, R* __restric
   Drone<R> s;
   R last[4];
   load_drone_full(v, n, s, last);
-  R qn[4], roll, pitch, yaw;
-  quat_readback(s.qx, s.qy, s.qz, s.qw, qn);
-  quat_to_euler(qn, roll, pitch, yaw);
-  o[0] = s.px; o[1] = s.py; o[2] = s.pz;
-  o[3] = qn[0]; o[4] = qn[1]; o[5] = qn[2]; o[6] = qn[3];
-  o[7] = roll; o[8] = pitch; o[9] = yaw;
-  o[10] = s.vx; o[11] = s.vy; o[12] = s.vz;
-  o[13] = s.ax; o[14] = s.ay; o[15] = s.az;
-  o[16] = last[0]; o[17] = last[1]; o[18] = last[2]; o[19] = last[3];
+  state20_store(s, last, o);
 }
 
 // Per-env non-finite guard: flag[e] = 1 when any drone of env e holds a
