@@ -133,11 +133,28 @@ def broadcast_params(module):
             off += p.numel()
 
 
-def make_env(multiagent, n_envs, act, physics, device, seed=0, distributed=False):
+def check_randomize(a):
+    """--randomize needs per-env drones: Physics.DYN on one GPU.  Exits before any GPU call."""
+    if a.randomize is None:
+        return
+    if Physics(a.physics) != Physics.DYN or a.gpus != 1:
+        raise SystemExit("learn.py: --randomize needs --physics dyn and --gpus 1 (per-env drone parameters and reset "
+                         "pools run the DYN integrator on one GPU; sharded vec envs do not take them)")
+    if a.pool < 1:
+        raise SystemExit("learn.py: --pool must be >= 1")
+
+
+def make_env(multiagent, n_envs, act, physics, device, seed=0, distributed=False, randomize=None, pool=256):
     env_cls = MultiHoverAviary if multiagent else HoverAviary
     kw = dict(obs=DEFAULT_OBS, act=act, physics=Physics(physics))
     if multiagent:
         kw["num_drones"] = DEFAULT_AGENTS
+    if randomize is not None:
+        # domain randomisation: every env starts as its own drone and becomes another one, drawn on
+        # the device from a pool, at each auto-reset
+        from gym_pybullet_drones_routing_amd.assets import randomized_params
+        kw["env_params"] = randomized_params(n_envs, randomize, seed)
+        kw["reset_pool"] = dict(env_params=randomized_params(pool, randomize, seed + 1), seed=seed)
     # store policy 2 (write-through rows): between the policy's kernels the step measured 6.12 vs
     # 6.40 us (bench.py rollout leg, profiles/r4/rollout_policy/); the back-to-back default is 3
     extra = {}
@@ -282,7 +299,8 @@ class FusedRollout:
 def train(multiagent=False, n_envs=4096, n_steps=64, total_timesteps=int(3e7), lr=3e-4, epochs=10,
           minibatch=16384, gamma=0.99, gae_lambda=0.95, clip=0.2, vf_coef=0.5, max_grad_norm=0.5,
           eval_every=1, seed=0, device="cuda:0", act=DEFAULT_ACT, target_reward=None, max_seconds=None,
-          log=print, physics=Physics.PYB, env=None, world=1, rank=0, graph=False, fused=False):
+          log=print, physics=Physics.PYB, env=None, world=1, rank=0, graph=False, fused=False, randomize=None,
+          pool=256):
     """PPO on the batched env.  ``env``: an already built torch-output VecEnv (e.g. the
     multi-GPU ``ShardedAviaryVecEnv``); by default one ``AviaryVecEnv`` on ``device``.
     world > 1: per-rank learners under torch.distributed — this rank trains on its own
@@ -296,7 +314,7 @@ def train(multiagent=False, n_envs=4096, n_steps=64, total_timesteps=int(3e7), l
     torch.manual_seed(seed)
     physics = Physics(physics)
     if env is None:
-        env = make_env(multiagent, n_envs, act, physics, device, seed)
+        env = make_env(multiagent, n_envs, act, physics, device, seed, randomize=randomize, pool=pool)
     if target_reward is None:   # learn.py:80-83
         if act == ActionType.ONE_D_RPM:
             target_reward = 474.15 if not multiagent else 949.5
@@ -444,6 +462,10 @@ def parse_args(argv=None):
     p.add_argument("--learner", default="rank0", choices=["rank0", "per-rank"],
                    help="rank0: one learner on the gathered batch (ShardedAviaryVecEnv); per-rank: a learner "
                         "per GPU on its own env shard, gradients all-reduced")
+    p.add_argument("--randomize", type=float, default=None, metavar="FRAC",
+                   help="domain randomisation (--physics dyn, --gpus 1): every env's drone parameters uniform in "
+                        "[1 - FRAC, 1 + FRAC] x nominal, and a new drone from a pool of --pool at each auto-reset")
+    p.add_argument("--pool", type=int, default=256, help="drones in the --randomize reset pool")
     return p.parse_args(argv)
 
 
@@ -490,7 +512,7 @@ def run(a):
     fused = a.rollout == "fused" and (world == 1 or getattr(env, "graphed", False))
     policy, hist, best, target = train(multiagent=multi, n_envs=a.n_envs, total_timesteps=int(a.total_timesteps),
                                        max_seconds=a.max_seconds, physics=Physics(a.physics), device=device, env=env,
-                                       graph=a.graph, seed=a.seed, fused=fused)
+                                       graph=a.graph, seed=a.seed, fused=fused, randomize=a.randomize, pool=a.pool)
     out = {"multiagent": multi, "physics": a.physics, "n_envs": a.n_envs, "gpus": world, "target_reward": target,
            "rollout": "fused" if fused else "eager",
            "best_eval_return": best, "reached": best >= target, "history": hist}
@@ -510,6 +532,7 @@ def _rank_entry(rank, world, port, argv):
 
 def main():
     a = parse_args()
+    check_randomize(a)
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is not None and int(env_world) != a.gpus:
         raise SystemExit(f"learn.py: WORLD_SIZE={env_world} but --gpus {a.gpus}")

@@ -38,7 +38,8 @@ EXPORTED = ("gpd_abi_version", "gpd_last_error", "gpd_default_params", "gpd_crea
             "gpd_default_pid_params", "gpd_set_pid_params", "gpd_get_ctrl_state", "gpd_set_ctrl_state",
             "gpd_nonfinite", "gpd_cmd_step", "gpd_cmd_rollout", "gpd_adjacency", "gpd_pack_layout_of", "gpd_handoff_pack",
             "gpd_handoff_unpack",
-            "gpd_create_het", "gpd_set_env_params", "gpd_set_env_init", "gpd_env_derive")
+            "gpd_create_het", "gpd_set_env_params", "gpd_set_env_init", "gpd_env_derive",
+            "gpd_set_reset_pool", "gpd_get_reset_draws", "gpd_get_env_table", "gpd_reset_pool_draw")
 
 # gpd_env_params: the per-env part of the drone parameters, in the struct's field order
 ENV_PARAM_NAMES = ("m", "arm", "thrust2weight", "ixx", "iyy", "izz", "kf", "km",
@@ -151,6 +152,10 @@ def load():
         "gpd_set_env_params": (ci, [vp, vp]),
         "gpd_set_env_init": (ci, [vp, vp, vp]),
         "gpd_env_derive": (ci, [ctypes.POINTER(DroneParams), vp, i, ctypes.POINTER(Constants)]),
+        "gpd_set_reset_pool": (ci, [vp, vp, i, vp, vp, i, ctypes.c_uint]),
+        "gpd_get_reset_draws": (ci, [vp, vp, vp]),
+        "gpd_get_env_table": (ci, [vp, vp]),
+        "gpd_reset_pool_draw": (ci, [ctypes.c_uint, i, ctypes.c_longlong, i, i]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(lib, name) and os.environ.get("GPD_ALLOW_ABI_MISMATCH"):

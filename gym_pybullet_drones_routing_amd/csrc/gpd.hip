@@ -143,6 +143,15 @@ struct gpd_sim {
   long long epad = 0;             // E rounded up to 64
   std::vector<gpd_env_params> env_rows;   // [E]
   std::vector<double> het_xyz, het_rpy;   // [E][D][3]
+  // reset pools (gpd_set_reset_pool; the pooled tail of step_kernel_het)
+  bool pool_on = false;           // step launches the pooled instantiation
+  int* d_draws = nullptr;         // [E][3] {episode number, row index, pose index}
+  void* d_pool = nullptr;         // ResetPool<real>: allocated at create, rewritten by every set
+  void* d_pool_rows = nullptr;    // [P][kHetCols]
+  void* d_pool_init = nullptr;    // [Q][D][10]
+  void* d_pool_target = nullptr;  // [Q][D][3]
+  std::vector<gpd_env_params> pool_rows;    // [P] host copies: fold_draws makes a drawn row / pose
+  std::vector<double> pool_xyz, pool_rpy;   // [Q][D][3] the env's own before the pool is replaced
 };
 
 namespace {
@@ -299,23 +308,28 @@ const void* step_fn_pid(bool multi, int flags) {
 }
 // het sims (gpd_step_het.h): the flag sets compiled in as step_fn_act chooses them (plain DYN,
 // ground effect + drag, downwash in multi-drone envs), the other DYN combinations at run time
-template <typename R, int ACT>
+// POOL: empty, or PoolArgs<R> for a sim with a reset pool (the same flag sets, the pooled tail)
+template <typename R, int ACT, typename... POOL>
 const void* step_het_fn_act(bool multi, int flags) {
   if (multi) {
     switch (flags) {
-      case 0: return (const void*)step_kernel_het<R, ACT, true, 0>;
-      case F_DW: return (const void*)step_kernel_het<R, ACT, true, F_DW>;
-      default: return (const void*)step_kernel_het<R, ACT, true, kPfRuntime>;
+      case 0: return (const void*)step_kernel_het<R, ACT, true, 0, POOL...>;
+      case F_DW: return (const void*)step_kernel_het<R, ACT, true, F_DW, POOL...>;
+      default: return (const void*)step_kernel_het<R, ACT, true, kPfRuntime, POOL...>;
     }
   }
   switch (flags) {
-    case 0: return (const void*)step_kernel_het<R, ACT, false, 0>;
-    case kPfAero: return (const void*)step_kernel_het<R, ACT, false, kPfAero>;
-    default: return (const void*)step_kernel_het<R, ACT, false, kPfRuntime>;
+    case 0: return (const void*)step_kernel_het<R, ACT, false, 0, POOL...>;
+    case kPfAero: return (const void*)step_kernel_het<R, ACT, false, kPfAero, POOL...>;
+    default: return (const void*)step_kernel_het<R, ACT, false, kPfRuntime, POOL...>;
   }
 }
 template <typename R>
 const void* step_kernel_fn(const gpd_sim* s) {
+  if (s->het && s->pool_on)
+    return s->cfg.act_type == GPD_ACT_RPM
+               ? step_het_fn_act<R, ACT_RPM, PoolArgs<R>>(s->D > 1, s->cfg.physics_flags)
+               : step_het_fn_act<R, ACT_ONE_D_RPM, PoolArgs<R>>(s->D > 1, s->cfg.physics_flags);
   if (s->het)
     return s->cfg.act_type == GPD_ACT_RPM ? step_het_fn_act<R, ACT_RPM>(s->D > 1, s->cfg.physics_flags)
                                           : step_het_fn_act<R, ACT_ONE_D_RPM>(s->D > 1, s->cfg.physics_flags);
@@ -358,14 +372,10 @@ size_t runtime_step_lds(int act, bool multi) {
   return fa.sharedSizeBytes;
 }
 
+// the LDS budget and dynamic-LDS attribute of the step kernel the sim launches (again when a reset
+// pool turns on or off: another instantiation)
 template <typename R>
-int upload_tables(gpd_sim* s) {
-  std::vector<R> ini(s->init_tmpl.begin(), s->init_tmpl.end());
-  std::vector<R> tgt(s->target.begin(), s->target.end());
-  const Consts<R> c = make_consts<R>(s);
-  HIP_TRY(hipMemcpy(s->d_init, ini.data(), ini.size() * sizeof(R), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(s->d_target, tgt.data(), tgt.size() * sizeof(R), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(s->d_consts, &c, sizeof(c), hipMemcpyHostToDevice));
+int prepare_step_kernel(gpd_sim* s) {
   if (s->wide) return GPD_OK;   // step_kernel_wide: no observation tile
   // the step kernel's static LDS (the PYB flag-set kernels park 44 KB of per-lane values around
   // the contact solve, gpd_device.h bullet_substep) beside the observation tile must fit the
@@ -390,6 +400,17 @@ int upload_tables(gpd_sim* s) {
   if (s->tile_bytes > 65536)
     HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, s->tile_bytes));
   return GPD_OK;
+}
+
+template <typename R>
+int upload_tables(gpd_sim* s) {
+  std::vector<R> ini(s->init_tmpl.begin(), s->init_tmpl.end());
+  std::vector<R> tgt(s->target.begin(), s->target.end());
+  const Consts<R> c = make_consts<R>(s);
+  HIP_TRY(hipMemcpy(s->d_init, ini.data(), ini.size() * sizeof(R), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->d_target, tgt.data(), tgt.size() * sizeof(R), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->d_consts, &c, sizeof(c), hipMemcpyHostToDevice));
+  return prepare_step_kernel<R>(s);
 }
 
 inline unsigned grid_for(long long n, int tpb) { return (unsigned)((n + tpb - 1) / tpb); }
@@ -453,6 +474,16 @@ int launch_step(gpd_sim* s, const float* actions, float* obs, float* reward, uin
   if (s->het) {
     typedef void (*HetFn)(R*, const float*, int2*, const Consts<R>*, const R*, int, int, long long, SimView<R>,
                           StepIO<R>);
+    if (s->pool_on) {
+      typedef void (*PoolFn)(R*, const float*, int2*, const Consts<R>*, const R*, int, int, long long, SimView<R>,
+                             StepIO<R>, PoolArgs<R>);
+      const PoolFn fp = (PoolFn)step_kernel_fn<R>(s);
+      const PoolArgs<R> pa{(const ResetPool<R>*)s->d_pool, s->d_draws};
+      hipLaunchKernelGGL(fp, dim3(grid), dim3(kWave), lds, st, v.state, io.actions, v.ctr, c, (const R*)s->d_etab,
+                         v.N, v.tpb, s->epad, v, io, pa);
+      HIP_TRY(hipGetLastError());
+      return GPD_OK;
+    }
     const HetFn fh = (HetFn)step_kernel_fn<R>(s);
     hipLaunchKernelGGL(fh, dim3(grid), dim3(kWave), lds, st, v.state, io.actions, v.ctr, c, (const R*)s->d_etab, v.N,
                        v.tpb, s->epad, v, io);
@@ -675,6 +706,11 @@ void free_sim(gpd_sim* s) {
   if (s->d_target) (void)hipFree(s->d_target);
   if (s->d_consts) (void)hipFree(s->d_consts);
   if (s->d_etab) (void)hipFree(s->d_etab);
+  if (s->d_draws) (void)hipFree(s->d_draws);
+  if (s->d_pool) (void)hipFree(s->d_pool);
+  if (s->d_pool_rows) (void)hipFree(s->d_pool_rows);
+  if (s->d_pool_init) (void)hipFree(s->d_pool_init);
+  if (s->d_pool_target) (void)hipFree(s->d_pool_target);
   if (s->d_dc_tab) (void)hipFree(s->d_dc_tab);
   if (s->d_dc_rows) (void)hipFree(s->d_dc_rows);
   delete s;
@@ -731,7 +767,7 @@ void derive_row(const gpd_drone_params& base, const gpd_env_params& r, gpd_const
   K.gnd_eff_h_clip = 0.25 * base.prop_radius * std::sqrt((15 * mr2 * r.kf * r.gnd_eff_coeff) / K.max_thrust);
 }
 
-int check_env_rows(const char* fn, const gpd_env_params* rows, int n) {
+int check_env_rows(const char* fn, const gpd_env_params* rows, int n, const char* unit = "env") {
   static const char* const names[11] = {"m", "arm", "thrust2weight", "ixx", "iyy", "izz", "kf", "km",
                                         "gnd_eff_coeff", "drag_coeff_xy", "drag_coeff_z"};
   for (int e = 0; e < n; ++e) {
@@ -739,7 +775,7 @@ int check_env_rows(const char* fn, const gpd_env_params* rows, int n) {
     for (int k = 0; k < 11; ++k) {
       const bool aero = k >= 8;   // the three aero coefficients may be 0
       if (!std::isfinite(f[k]) || f[k] < 0.0 || (!aero && f[k] == 0.0))
-        return fail(GPD_EINVAL, std::string(fn) + ": env_params field " + names[k] + " of env " + std::to_string(e) +
+        return fail(GPD_EINVAL, std::string(fn) + ": env_params field " + names[k] + " of " + unit + " " + std::to_string(e) +
                                     " must be finite and " + (aero ? ">= 0" : "> 0"));
     }
   }
@@ -747,24 +783,23 @@ int check_env_rows(const char* fn, const gpd_env_params* rows, int n) {
 }
 static_assert(sizeof(gpd_env_params) == 11 * sizeof(double), "gpd_env_params is 11 packed doubles");
 
-int check_poses(const char* fn, const char* what, const double* p, long long n_drones, int D) {
+int check_poses(const char* fn, const char* what, const double* p, long long n_drones, int D, const char* unit = "env") {
   if (!p) return GPD_OK;
   for (long long i = 0; i < n_drones * 3; ++i)
     if (!std::isfinite(p[i]))
-      return fail(GPD_EINVAL, std::string(fn) + ": " + what + " of env " + std::to_string(i / (3LL * D)) +
+      return fail(GPD_EINVAL, std::string(fn) + ": " + what + " of " + unit + " " + std::to_string(i / (3LL * D)) +
                                   " drone " + std::to_string((i / 3) % D) + " is not finite");
   return GPD_OK;
 }
 
-// [E][D][10] templates and [E][D][3] targets from the stored het poses
-void het_templates(gpd_sim* s) {
-  const int task = s->cfg.task;
-  for (int e = 0; e < s->E; ++e)
-    for (int d = 0; d < s->D; ++d) {
-      const size_t n = (size_t)e * s->D + d;
-      const double* xyz = &s->het_xyz[n * 3];
-      pose_template(xyz, &s->het_rpy[n * 3], &s->init_tmpl[n * 10]);
-      double* tg = &s->target[n * 3];
+// [n][D][10] templates and [n][D][3] targets from n x D poses (a het sim's envs, or a reset pool)
+void pose_tables(int task, size_t n_sets, int D, const double* xyzs, const double* rpys, double* tmpl, double* target) {
+  for (size_t e = 0; e < n_sets; ++e)
+    for (int d = 0; d < D; ++d) {
+      const size_t n = e * D + d;
+      const double* xyz = &xyzs[n * 3];
+      pose_template(xyz, &rpys[n * 3], &tmpl[n * 10]);
+      double* tg = &target[n * 3];
       tg[0] = tg[1] = tg[2] = 0.0;
       if (task == GPD_TASK_HOVER) {           // HoverAviary.py:51
         tg[2] = 1.0;
@@ -773,25 +808,104 @@ void het_templates(gpd_sim* s) {
       }
     }
 }
+// [E][D][10] templates and [E][D][3] targets from the stored het poses
+void het_templates(gpd_sim* s) {
+  pose_tables(s->cfg.task, (size_t)s->E, s->D, s->het_xyz.data(), s->het_rpy.data(), s->init_tmpl.data(),
+              s->target.data());
+}
 
-// the per-env constant table: derived in double with make_consts' expressions, rounded once to R
+// the kHetCols constants of one row: derived in double with make_consts' expressions, rounded once
+// to R; put(col, value) places them (the env table's SoA columns, a reset pool's row-major rows)
+template <typename R, typename Put>
+void env_row_consts(const gpd_drone_params& base, const gpd_env_params& r, Put put) {
+  gpd_constants K;
+  derive_row(base, r, K);
+  put(kHetM, (R)r.m); put(kHetGravity, (R)K.gravity); put(kHetInvM, (R)(1.0 / r.m));
+  put(kHetKf, (R)r.kf); put(kHetKm, (R)r.km); put(kHetL, (R)r.arm); put(kHetLs2, (R)(r.arm / std::sqrt(2.0)));
+  put(kHetJx, (R)r.ixx); put(kHetJy, (R)r.iyy); put(kHetJz, (R)r.izz);
+  put(kHetIjx, (R)(1.0 / r.ixx)); put(kHetIjy, (R)(1.0 / r.iyy)); put(kHetIjz, (R)(1.0 / r.izz));
+  put(kHetHover, (R)(double)(float)K.hover_rpm);   // float32(HOVER_RPM), exact in either real type
+  put(kHetGeCoeff, (R)r.gnd_eff_coeff); put(kHetGeClip, (R)K.gnd_eff_h_clip);
+  put(kHetDragXy, (R)r.drag_coeff_xy); put(kHetDragZ, (R)r.drag_coeff_z);
+}
+
+// the per-env constant table
 template <typename R>
 int upload_env_table(gpd_sim* s) {
   std::vector<R> tab((size_t)kHetCols * s->epad, R(0));
-  for (int e = 0; e < s->E; ++e) {
-    const gpd_env_params& r = s->env_rows[e];
-    gpd_constants K;
-    derive_row(s->P, r, K);
-    auto put = [&](int col, double v) { tab[(size_t)col * s->epad + e] = (R)v; };
-    put(kHetM, r.m); put(kHetGravity, K.gravity); put(kHetInvM, 1.0 / r.m);
-    put(kHetKf, r.kf); put(kHetKm, r.km); put(kHetL, r.arm); put(kHetLs2, r.arm / std::sqrt(2.0));
-    put(kHetJx, r.ixx); put(kHetJy, r.iyy); put(kHetJz, r.izz);
-    put(kHetIjx, 1.0 / r.ixx); put(kHetIjy, 1.0 / r.iyy); put(kHetIjz, 1.0 / r.izz);
-    put(kHetHover, (double)(float)K.hover_rpm);   // float32(HOVER_RPM), exact in either real type
-    put(kHetGeCoeff, r.gnd_eff_coeff); put(kHetGeClip, K.gnd_eff_h_clip);
-    put(kHetDragXy, r.drag_coeff_xy); put(kHetDragZ, r.drag_coeff_z);
-  }
+  for (int e = 0; e < s->E; ++e)
+    env_row_consts<R>(s->P, s->env_rows[e], [&](int col, R v) { tab[(size_t)col * s->epad + e] = v; });
   HIP_TRY(hipMemcpy(s->d_etab, tab.data(), tab.size() * sizeof(R), hipMemcpyHostToDevice));
+  return GPD_OK;
+}
+
+// ---- reset pools (gpd_set_reset_pool)
+// Drawn rows / poses become the env's own (host copies included) and every index goes back to -1;
+// the episode numbers stay.  Called, after a device synchronise, before anything replaces the
+// pools or the env tables.  which: bit 0 rows, bit 1 poses.
+int fold_draws(gpd_sim* s, int which) {
+  std::vector<int> dr((size_t)s->E * 3);
+  HIP_TRY(hipMemcpy(dr.data(), s->d_draws, dr.size() * sizeof(int), hipMemcpyDeviceToHost));
+  const size_t D3 = (size_t)s->D * 3;
+  for (int e = 0; e < s->E; ++e) {
+    int* d = &dr[(size_t)e * 3];
+    if ((which & 1) && d[1] >= 0) {
+      if ((size_t)d[1] < s->pool_rows.size()) s->env_rows[e] = s->pool_rows[d[1]];
+      d[1] = -1;
+    }
+    if ((which & 2) && d[2] >= 0) {
+      if (((size_t)d[2] + 1) * D3 <= s->pool_xyz.size()) {
+        std::copy_n(&s->pool_xyz[d[2] * D3], D3, &s->het_xyz[e * D3]);
+        std::copy_n(&s->pool_rpy[d[2] * D3], D3, &s->het_rpy[e * D3]);
+      }
+      d[2] = -1;
+    }
+  }
+  HIP_TRY(hipMemcpy(s->d_draws, dr.data(), dr.size() * sizeof(int), hipMemcpyHostToDevice));
+  return GPD_OK;
+}
+
+template <typename R>
+int upload_pool(gpd_sim* s, unsigned seed) {
+  const int P = (int)s->pool_rows.size(), D = s->D;
+  const size_t Q = s->pool_xyz.size() / ((size_t)D * 3);
+  std::vector<R> rows((size_t)P * kHetCols);
+  for (int i = 0; i < P; ++i)
+    env_row_consts<R>(s->P, s->pool_rows[i], [&](int col, R v) { rows[(size_t)i * kHetCols + col] = v; });
+  std::vector<double> tmpl(Q * D * 10), tgt(Q * D * 3);
+  pose_tables(s->cfg.task, Q, D, s->pool_xyz.data(), s->pool_rpy.data(), tmpl.data(), tgt.data());
+  const std::vector<R> ini(tmpl.begin(), tmpl.end()), tg(tgt.begin(), tgt.end());
+  for (void** p : {&s->d_pool_rows, &s->d_pool_init, &s->d_pool_target}) {
+    if (*p) HIP_TRY(hipFree(*p));
+    *p = nullptr;
+  }
+  if (P > 0) {
+    HIP_TRY(hipMalloc(&s->d_pool_rows, rows.size() * sizeof(R)));
+    HIP_TRY(hipMemcpy(s->d_pool_rows, rows.data(), rows.size() * sizeof(R), hipMemcpyHostToDevice));
+  }
+  if (Q > 0) {
+    HIP_TRY(hipMalloc(&s->d_pool_init, ini.size() * sizeof(R)));
+    HIP_TRY(hipMalloc(&s->d_pool_target, tg.size() * sizeof(R)));
+    HIP_TRY(hipMemcpy(s->d_pool_init, ini.data(), ini.size() * sizeof(R), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->d_pool_target, tg.data(), tg.size() * sizeof(R), hipMemcpyHostToDevice));
+  }
+  const ResetPool<R> desc{(const R*)s->d_pool_rows, (const R*)s->d_pool_init, (const R*)s->d_pool_target, P, (int)Q,
+                          seed};
+  HIP_TRY(hipMemcpy(s->d_pool, &desc, sizeof(desc), hipMemcpyHostToDevice));
+  const bool on = P > 0 || Q > 0;
+  if (on != s->pool_on) {   // another step kernel instantiation: its LDS budget and attribute
+    s->pool_on = on;
+    return prepare_step_kernel<R>(s);
+  }
+  return GPD_OK;
+}
+
+template <typename R>
+int env_table_to_host(gpd_sim* s, double* out) {
+  std::vector<R> tab((size_t)kHetCols * s->epad);
+  HIP_TRY(hipMemcpy(tab.data(), s->d_etab, tab.size() * sizeof(R), hipMemcpyDeviceToHost));
+  for (int e = 0; e < s->E; ++e)
+    for (int c = 0; c < kHetCols; ++c) out[(size_t)e * kHetCols + c] = (double)tab[(size_t)c * s->epad + e];
   return GPD_OK;
 }
 
@@ -889,6 +1003,8 @@ int gpd_set_env_params(gpd_sim* sim, const gpd_env_params* rows_host) {
   rc = settle_last_any(sim, 0);
   if (rc != GPD_OK) return rc;
   HIP_TRY(hipDeviceSynchronize());
+  rc = fold_draws(sim, 1);   // every row index back to -1: the rows in force are the new ones
+  if (rc != GPD_OK) return rc;
   sim->env_rows.assign(rows_host, rows_host + sim->E);
   return sim->prec == GPD_F64 ? upload_env_table<double>(sim) : upload_env_table<float>(sim);
 }
@@ -900,6 +1016,8 @@ int gpd_set_env_init(gpd_sim* sim, const double* xyzs_host, const double* rpys_h
   if (rc == GPD_OK) rc = check_poses("gpd_set_env_init", "init_rpys", rpys_host, sim->N, sim->D);
   if (rc != GPD_OK) return rc;
   HIP_TRY(hipDeviceSynchronize());
+  rc = fold_draws(sim, 2);   // a NULL table keeps the poses in force; every pose index back to -1
+  if (rc != GPD_OK) return rc;
   if (xyzs_host) sim->het_xyz.assign(xyzs_host, xyzs_host + (size_t)sim->N * 3);
   if (rpys_host) sim->het_rpy.assign(rpys_host, rpys_host + (size_t)sim->N * 3);
   het_templates(sim);
@@ -910,6 +1028,48 @@ int gpd_env_derive(const gpd_drone_params* base, const gpd_env_params* rows, int
   if (!base || !rows || !out || n < 0) return fail(GPD_EINVAL, "gpd_env_derive: NULL argument or n < 0");
   for (int i = 0; i < n; ++i) derive_row(*base, rows[i], out[i]);
   return GPD_OK;
+}
+
+int gpd_reset_pool_draw(unsigned seed, int stream, long long env, int episode, int n) {
+  if (n < 1) return 0;
+  return pool_draw(seed, (unsigned)stream, (unsigned)env, (unsigned)episode, (unsigned)n);
+}
+
+int gpd_set_reset_pool(gpd_sim* sim, const gpd_env_params* rows_host, int n_rows, const double* xyzs_host,
+                       const double* rpys_host, int n_poses, unsigned seed) {
+  if (!sim) return fail(GPD_EINVAL, "gpd_set_reset_pool: NULL sim");
+  if (!sim->het) return fail(GPD_EINVAL, "gpd_set_reset_pool: not a het sim (create it with gpd_create_het)");
+  if (n_rows < 0 || n_poses < 0) return fail(GPD_EINVAL, "gpd_set_reset_pool: n_rows and n_poses must be >= 0");
+  if (n_rows > 0 && !rows_host) return fail(GPD_EINVAL, "gpd_set_reset_pool: rows_host is NULL but n_rows > 0");
+  if (n_poses > 0 && !xyzs_host) return fail(GPD_EINVAL, "gpd_set_reset_pool: xyzs_host is NULL but n_poses > 0");
+  const long long nq = (long long)n_poses * sim->D;
+  int rc = check_env_rows("gpd_set_reset_pool", rows_host, n_rows, "pool row");
+  if (rc == GPD_OK) rc = check_poses("gpd_set_reset_pool", "xyzs", n_poses ? xyzs_host : nullptr, nq, sim->D, "pool pose");
+  if (rc == GPD_OK) rc = check_poses("gpd_set_reset_pool", "rpys", n_poses ? rpys_host : nullptr, nq, sim->D, "pool pose");
+  if (rc != GPD_OK) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  rc = fold_draws(sim, 3);   // what the old pools gave stays in force, as the env's own
+  if (rc != GPD_OK) return rc;
+  sim->pool_rows.assign(rows_host, rows_host + n_rows);
+  sim->pool_xyz.assign(xyzs_host, xyzs_host + nq * 3);
+  if (n_poses && rpys_host) sim->pool_rpy.assign(rpys_host, rpys_host + nq * 3);
+  else sim->pool_rpy.assign((size_t)nq * 3, 0.0);
+  return sim->prec == GPD_F64 ? upload_pool<double>(sim, seed) : upload_pool<float>(sim, seed);
+}
+
+int gpd_get_reset_draws(gpd_sim* sim, int* out_dev, void* stream) {
+  if (!sim || !out_dev) return fail(GPD_EINVAL, "gpd_get_reset_draws: NULL argument");
+  if (!sim->het) return fail(GPD_EINVAL, "gpd_get_reset_draws: not a het sim (create it with gpd_create_het)");
+  HIP_TRY(hipMemcpyAsync(out_dev, sim->d_draws, (size_t)sim->E * 3 * sizeof(int), hipMemcpyDeviceToDevice,
+                         (hipStream_t)stream));
+  return GPD_OK;
+}
+
+int gpd_get_env_table(gpd_sim* sim, double* out_host) {
+  if (!sim || !out_host) return fail(GPD_EINVAL, "gpd_get_env_table: NULL argument");
+  if (!sim->het) return fail(GPD_EINVAL, "gpd_get_env_table: not a het sim (create it with gpd_create_het)");
+  HIP_TRY(hipDeviceSynchronize());
+  return sim->prec == GPD_F64 ? env_table_to_host<double>(sim, out_host) : env_table_to_host<float>(sim, out_host);
 }
 
 }  // extern "C"
@@ -1168,6 +1328,9 @@ int create_impl(const gpd_drone_params* params, const gpd_config* cfg, const Het
   hipError_t e6 = hipMalloc(&s->d_consts, s->prec == GPD_F64 ? sizeof(Consts<double>) : sizeof(Consts<float>));
   hipError_t e7 = pid ? hipMalloc(&s->d_ctrl, (size_t)kCtrlComps * s->npad * rs) : hipSuccess;
   hipError_t e8 = s->het ? hipMalloc(&s->d_etab, (size_t)kHetCols * s->epad * rs) : hipSuccess;
+  if (s->het && e8 == hipSuccess) e8 = hipMalloc((void**)&s->d_draws, (size_t)s->E * 3 * sizeof(int));
+  if (s->het && e8 == hipSuccess)
+    e8 = hipMalloc(&s->d_pool, s->prec == GPD_F64 ? sizeof(ResetPool<double>) : sizeof(ResetPool<float>));
   if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess ||
       e6 != hipSuccess || e7 != hipSuccess || e8 != hipSuccess) {
     free_sim(s);
@@ -1211,6 +1374,13 @@ int create_impl(const gpd_drone_params* params, const gpd_config* cfg, const Het
   }
   int rc = s->prec == GPD_F64 ? upload_tables<double>(s) : upload_tables<float>(s);
   if (rc == GPD_OK && s->het) rc = s->prec == GPD_F64 ? upload_env_table<double>(s) : upload_env_table<float>(s);
+  if (rc == GPD_OK && s->het) {   // no pool; every env in episode 0 on its own row and pose
+    std::vector<int> dr((size_t)s->E * 3, -1);
+    for (int e = 0; e < s->E; ++e) dr[(size_t)e * 3] = 0;
+    if (hipMemset(s->d_pool, 0, s->prec == GPD_F64 ? sizeof(ResetPool<double>) : sizeof(ResetPool<float>)) != hipSuccess ||
+        hipMemcpy(s->d_draws, dr.data(), dr.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+      rc = fail(GPD_EHIP, "gpd_create_het: reset pool state");
+  }
   if (rc != GPD_OK) { free_sim(s); return rc; }
   if (hipMemset(s->d_state, 0, (size_t)kStateComps * s->npad * rs) != hipSuccess ||
       hipMemset(s->d_ring, 0, (size_t)s->ring_len * s->npad * s->A * sizeof(float)) != hipSuccess ||

@@ -18,6 +18,14 @@
 // flight); single-drone envs read 64 consecutive elements per column.  The downwash coefficients
 // stay sim-wide: in the thin-block pair path (substep_block, pairs.n > 0) a lane evaluates dw_pair
 // for a drone of ANOTHER env, so they must come from the shared constant block.
+//
+// Reset pools (gpd_set_reset_pool): a pool of P drones (rows [P][kHetCols], row-major: one lane
+// reads one row) and a pool of Q start poses (templates [Q][D][10], targets [Q][D][3]), derived on
+// the host by the code that derives the tables above.  The pooled instantiations of step_kernel_het
+// (POOL = one PoolArgs) give an env that auto-resets its next drone and pose: pool_draw, a pure
+// function of (seed, env, episode number), picks the indices; the env's own lanes copy the row
+// into etab[:, e] and the pose into init[e] / target[e].  draws [E][3] int32 holds {episode number,
+// row index in force, pose index in force}, -1 = the env's own (not drawn) value.
 #pragma once
 #include "gpd_step.h"
 
@@ -55,15 +63,53 @@ __device__ __forceinline__ Consts<R> het_consts(const Consts<R>& c, const R* __r
   return lc;
 }
 
+// The pool draw (gpd_reset_pool_draw is this function): uint32 arithmetic, then one 32x32 -> 64
+// multiply that maps the hash to [0, n).  stream: 1 = parameter rows, 2 = poses; k: the env's
+// episode number (1 at its first auto-reset).
+__host__ __device__ __forceinline__ unsigned pool_mix32(unsigned x) {
+  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+  return x;
+}
+__host__ __device__ __forceinline__ int pool_draw(unsigned seed, unsigned stream, unsigned e, unsigned k, unsigned n) {
+  unsigned h = pool_mix32(seed ^ (0x9e3779b9u * stream));
+  h = pool_mix32(h + e);
+  h = pool_mix32(h + k);
+  return (int)(((unsigned long long)h * n) >> 32);
+}
+enum : unsigned { kPoolStreamRows = 1, kPoolStreamPoses = 2 };
+template <typename T, typename... Rest>
+__device__ __forceinline__ const T& first_arg(const T& a, const Rest&...) { return a; }
+
+// The pool descriptor, in device memory at an address that never changes: replacing a pool by
+// another of any size rewrites these fields and leaves a captured graph valid.
+template <typename R>
+struct ResetPool {
+  const R* rows;     // [P][kHetCols]
+  const R* init;     // [Q][D][10]
+  const R* target;   // [Q][D][3]
+  int P, Q;          // 0: parameters / poses are never redrawn
+  unsigned seed;
+};
+template <typename R>
+struct PoolArgs {
+  const ResetPool<R>* pool;
+  int* draws;        // [E][3]
+};
+
 // ---------------------------------------------------------------------------------------
 // gpd_step of a het sim: step_kernel's phases (gpd_step.h) with the lane's own constants, reset
 // template (v.init + nn*10) and task target (v.target + nn*3), and no drone contact.  PF as in
 // step_kernel: 0, F_GND|F_DRAG, F_DW (multi) compiled in, kPfRuntime for the other DYN flag sets.
-template <typename R, int ACT, bool MULTI, int PF>
+// POOL is empty (a sim without a reset pool: the kernel and its arguments as they always were) or
+// one PoolArgs<R> (the pooled instantiation: the same code plus the pooled tail below).
+template <typename R, int ACT, bool MULTI, int PF, typename... POOL>
 __global__ __launch_bounds__(kWave) void step_kernel_het(R* __restrict__ state_p, const float* __restrict__ actions_p,
                                                          int2* __restrict__ ctr_p, const Consts<R>* __restrict__ cp,
                                                          const R* __restrict__ etab, int n_p, int tpb_p,
-                                                         long long epad, SimView<R> v, StepIO<R> io) {
+                                                         long long epad, SimView<R> v, StepIO<R> io,
+                                                         POOL... pool_args) {
+  static_assert(sizeof...(POOL) <= 1, "POOL is empty or one PoolArgs<R>");
+  constexpr bool kPool = sizeof...(POOL) == 1;
   static_assert(!act_is_pid(ACT), "het sims take the RPM action types only");
   static_assert(PF == kPfRuntime || (PF & ~kHetFlags) == 0, "het sims run the DYN integrator only");
   v.state = state_p; v.ctr = ctr_p; v.N = n_p; v.tpb = tpb_p;
@@ -97,6 +143,17 @@ __global__ __launch_bounds__(kWave) void step_kernel_het(R* __restrict__ state_p
   const int2 cv = v.ctr[e];
   const int sc = cv.x;        // step_counter
   const int head = cv.y;      // ring slot receiving this step's action
+  // pooled: the env's draws and the pool descriptor in the entry batch of loads, so that the
+  // pooled tail does not start with two dependent round trips (descriptor, then draws)
+  ResetPool<R> pool = {};
+  int* draws_e = nullptr;
+  int episode = 0, pi = -1, qi = -1;
+  if constexpr (kPool) {
+    const PoolArgs<R> pa = first_arg(pool_args...);
+    pool = *pa.pool;
+    draws_e = pa.draws + e * 3;
+    episode = draws_e[0]; pi = draws_e[1]; qi = draws_e[2];
+  }
   float a[A];
   action_load<A>(io.actions, nn, a);
 
@@ -159,9 +216,67 @@ __global__ __launch_bounds__(kWave) void step_kernel_het(R* __restrict__ state_p
   if (active) ring_append<A>(v.ring, n, head, v.ring_len, a);
 
   const int NC = A == 4 ? 3 + v.ring_len : 12 + v.ring_len * A;  // tile columns (float4 / float)
+  const R* tmpl = v.init + nn * 10;   // the drone's own start pose
+  if constexpr (kPool) {
+    // The pooled tail: the env's next drone and pose.  The reward, flags and terminal row above are
+    // the old drone's and the old target's.  The branch is wave-uniform and, at real episode
+    // lengths, skipped by almost every wave.  Only lanes of env e's own block ever read or write
+    // env e's columns of etab, init, target and draws, and they read them at the kernel's entry,
+    // so no ordering against other blocks is needed; the next launch sees the stores.
+    // The lane then resets itself through ONE reset_to_template call on a selected pointer.  That
+    // form is the one found to leave the substeps' rounding alone: with the drawn template handed
+    // over in registers (a second call, or an override after the plain call), and also with the
+    // state pinned by an empty asm in front of the tail, some instantiation (f64 gnd + drag, f64
+    // plain, f32 gnd + drag) came out one ulp away from its non-pooled twin on nominal rows, as the
+    // note at the substep loop above describes; tests/test_gpu_pool.py holds every instantiation
+    // family to bit-equality.
+    if (__ballot(do_reset && active) != 0ull) {
+      const bool mine = do_reset && active;
+      const bool new_row = mine && d == 0 && pool.P > 0;
+      const bool new_pose = mine && pool.Q > 0;
+      // every lane of the env makes the env's draws itself: a pure function of (seed, e, episode)
+      const unsigned k = (unsigned)episode + 1u;
+      if (pool.P > 0) pi = pool_draw(pool.seed, kPoolStreamRows, (unsigned)e, k, (unsigned)pool.P);
+      if (pool.Q > 0) qi = pool_draw(pool.seed, kPoolStreamPoses, (unsigned)e, k, (unsigned)pool.Q);
+      // all of the copies' loads first (one round trip), then their stores
+      R prow[kHetCols], ptmpl[10], ptgt[3];
+      const long long q = (long long)qi * D + d;
+      if (new_row) {
+        const R* row = pool.rows + (long long)pi * kHetCols;
+#pragma unroll
+        for (int c2 = 0; c2 < kHetCols; ++c2) prow[c2] = row[c2];
+      }
+      if (new_pose) {
+        tmpl = pool.init + q * 10;   // the drawn start pose
+#pragma unroll
+        for (int c2 = 0; c2 < 10; ++c2) ptmpl[c2] = pool.init[q * 10 + c2];
+#pragma unroll
+        for (int c2 = 0; c2 < 3; ++c2) ptgt[c2] = pool.target[q * 3 + c2];
+      }
+      if (new_row) {
+        // etab[:, e] <- the pool row (ordinary vector stores).  last_clipped_action needs no
+        // care: the env's hover column changes only here, at a reset, where the step counter
+        // becomes 0 and last_from_ring_kernel / settle_last_any therefore write 0 whatever
+        // the hover column holds; the next step stores a last action made with the new one.
+        R* col = const_cast<R*>(etab) + e;
+#pragma unroll
+        for (int c2 = 0; c2 < kHetCols; ++c2) col[c2 * epad] = prow[c2];
+      }
+      if (new_pose) {
+        // init[e][d] / target[e][d] <- the drawn pose: gpd_reset goes back to the pose in force
+        R* ini = const_cast<R*>(v.init) + nn * 10;
+        R* tgt = const_cast<R*>(v.target) + nn * 3;
+#pragma unroll
+        for (int c2 = 0; c2 < 10; ++c2) ini[c2] = ptmpl[c2];
+#pragma unroll
+        for (int c2 = 0; c2 < 3; ++c2) tgt[c2] = ptgt[c2];
+      }
+      if (mine && d == 0) { draws_e[0] = (int)k; draws_e[1] = pi; draws_e[2] = qi; }
+    }
+  }
   if (do_reset) {
     if (active && io.terminal_obs != nullptr) row12_store<A>(io.terminal_obs + n * v.W, row12);
-    reset_to_template(v.init + nn * 10, s, last, row12);   // the drone's own start pose
+    reset_to_template(tmpl, s, last, row12);
   }
   const unsigned long long done_rows = __ballot(do_reset && active && io.terminal_obs != nullptr);
 

@@ -26,7 +26,7 @@ class AviaryVecEnv(_VecEnvBase):
     def __init__(self, num_envs, task="hover", num_drones=1, drone_model=DroneModel.CF2X, initial_xyzs=None,
                  initial_rpys=None, physics=Physics.DYN, aero=(), pyb_freq=240, ctrl_freq=30,
                  obs=ObservationType.KIN, act=ActionType.RPM, precision="f64", device=None, output="numpy",
-                 episode_len_sec=8, urdf_path=None, tuning=None, env_params=None):
+                 episode_len_sec=8, urdf_path=None, tuning=None, env_params=None, reset_pool=None):
         if ObservationType(obs) != ObservationType.KIN:
             raise NotImplementedError("ObservationType.RGB is out of scope")
         if output not in ("numpy", "torch"):
@@ -37,7 +37,8 @@ class AviaryVecEnv(_VecEnvBase):
                                     urdf_path=urdf_path, pyb_freq=pyb_freq, ctrl_freq=ctrl_freq, act=act,
                                     task=task, physics=physics, aero=aero, precision=precision, autoreset=True,
                                     episode_len_sec=episode_len_sec, initial_xyzs=initial_xyzs,
-                                    initial_rpys=initial_rpys, device=device, tuning=tuning, env_params=env_params)
+                                    initial_rpys=initial_rpys, device=device, tuning=tuning, env_params=env_params,
+                                    reset_pool=reset_pool)
         self.num_envs = int(num_envs)
         self.num_drones = int(num_drones)
         self.output = output
@@ -119,7 +120,8 @@ def make_vec_env(env_cls, n_envs=1, seed=None, env_kwargs=None, distributed=Fals
     """``stable_baselines3.common.env_util.make_vec_env`` stand-in for the two RL aviaries:
     builds ONE batched ``AviaryVecEnv`` instead of ``n_envs`` Python env objects (``env_params`` and
     (E, D, 3) ``initial_xyzs`` / ``initial_rpys`` in ``env_kwargs`` make its envs differ, as the
-    reference's env objects may; they need ``physics=Physics.DYN``, the default here is PYB); with
+    reference's env objects may, ``reset_pool`` gives each a new drone and start pose at every
+    auto-reset; they need ``physics=Physics.DYN``, the default here is PYB); with
     ``distributed=True`` (inside an initialised torch.distributed group) a
     ``ShardedAviaryVecEnv`` whose envs are split over the group's ranks."""
     from .HoverAviary import HoverAviary
@@ -136,9 +138,9 @@ def make_vec_env(env_cls, n_envs=1, seed=None, env_kwargs=None, distributed=Fals
     kw.setdefault("physics", Physics.PYB)   # the env classes' default (HoverAviary.py:20, MultiHoverAviary.py:22)
     if distributed:
         both = {**kw, **vec_kwargs}
-        if both.get("env_params") is not None or any(
+        if both.get("env_params") is not None or both.get("reset_pool") is not None or any(
                 both.get(k) is not None and np.ndim(both[k]) == 3 for k in ("initial_xyzs", "initial_rpys")):
-            raise NotImplementedError("per-env parameters and (E, D, 3) start poses are not supported by "
+            raise NotImplementedError("per-env parameters, reset pools and (E, D, 3) start poses are not supported by "
                                       "ShardedAviaryVecEnv")
         return ShardedAviaryVecEnv(n_envs, task=task, num_drones=nd, **kw, **vec_kwargs)
     return AviaryVecEnv(n_envs, task=task, num_drones=nd, **kw, **vec_kwargs)

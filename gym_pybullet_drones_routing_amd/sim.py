@@ -173,6 +173,27 @@ def env_derive(params, rows):
     return {name: np.array([getattr(out[i], name) for i in range(n)], dtype=np.float64) for name in _DERIVED}
 
 
+def _mix32(x):
+    x ^= x >> 16
+    x = (x * 0x7feb352d) & 0xffffffff
+    x ^= x >> 15
+    x = (x * 0x846ca68b) & 0xffffffff
+    return x ^ (x >> 16)
+
+
+def reset_pool_draw(seed, stream, env, episode, n):
+    """``gpd_reset_pool_draw`` restated in Python ints: the index in [0, n) that env ``env`` draws
+    at its ``episode``-th auto-reset from a reset pool of ``n`` entries (``stream`` 1: parameter
+    rows, 2: poses).  uint32 arithmetic, then one 32x32 -> 64 multiply."""
+    seed, stream, env, episode, n = int(seed), int(stream), int(env), int(episode), int(n)
+    if n < 1:
+        return 0
+    h = _mix32((seed ^ (0x9e3779b9 * stream)) & 0xffffffff)
+    h = _mix32((h + env) & 0xffffffff)
+    h = _mix32((h + episode) & 0xffffffff)
+    return (h * n) >> 32
+
+
 class BatchedAviarySim:
     """``n_envs`` x ``drones_per_env`` Crazyflie-class drones stepped in lockstep on one GPU.
 
@@ -180,15 +201,21 @@ class BatchedAviarySim:
     ``initial_xyzs`` / ``initial_rpys`` of shape (E, D, 3) make the sim heterogeneous (``sim.het``):
     every env with its own drone parameters, every drone of every env with its own start pose
     (``gpd_create_het``).  Het sims run Physics.DYN (with any of the gnd / drag / dw / geom terms) and
-    the RPM action types; anything else raises NotImplementedError."""
+    the RPM action types; anything else raises NotImplementedError.
+
+    ``reset_pool=dict(env_params={name: array[P]}, initial_xyzs=(Q, D, 3), initial_rpys=(Q, D, 3),
+    seed=0)`` (every key optional) also makes the sim heterogeneous and gives each env a new drone and
+    start pose, drawn from the pools on the device, at every auto-reset (:meth:`set_reset_pool`)."""
 
     def __init__(self, n_envs, drones_per_env=1, drone_model=DroneModel.CF2X, urdf_path=None,
                  pyb_freq=240, ctrl_freq=30, act=ActionType.RPM, task="hover",
                  physics=Physics.DYN, aero=(), precision="f64", autoreset=True, episode_len_sec=8,
-                 initial_xyzs=None, initial_rpys=None, device=None, tuning=None, env_params=None):
+                 initial_xyzs=None, initial_rpys=None, device=None, tuning=None, env_params=None,
+                 reset_pool=None):
         self._lib = _lib.load()
         act = ActionType(act)
-        if env_params is not None or any(a is not None and np.ndim(a) == 3 for a in (initial_xyzs, initial_rpys)):
+        if env_params is not None or reset_pool is not None \
+                or any(a is not None and np.ndim(a) == 3 for a in (initial_xyzs, initial_rpys)):
             # a heterogeneous sim: what it cannot run is refused, never silently dropped
             if physics_flags(physics, aero) & _lib.GPD_F_BULLET:
                 raise NotImplementedError(
@@ -257,7 +284,8 @@ class BatchedAviarySim:
                 keep.append(a)
                 setattr(cfg, name, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
         self.physics_flags = cfg.physics_flags
-        self.het = env_params is not None or bool(het_poses)
+        self.het = env_params is not None or bool(het_poses) or reset_pool is not None
+        self._pool_rows = np.empty((0, len(_lib.ENV_PARAM_NAMES)))
         handle = ctypes.c_void_p()
         if self.het:
             self._env_rows = env_param_rows(self.params, self.n_envs, env_params)
@@ -301,6 +329,8 @@ class BatchedAviarySim:
         self._tobs_ptr = _ptr(self.terminal_obs)
         self._obs20 = None              # cmd_step's [E, D, 20] rows, allocated on first use (not in out_pack)
         self.reset()
+        if reset_pool is not None:
+            self.set_reset_pool(reset_pool)
 
     # ------------------------------------------------------------------ heterogeneous sims
     def _pose_table(self, arr):
@@ -318,7 +348,7 @@ class BatchedAviarySim:
         {name: array[E]}; names it leaves out keep their current per-env values.  A synchronous
         upload that changes no launch geometry: a captured graph stays valid.  Acts from the next step."""
         self._need_het("set_env_params")
-        rows = self._env_rows.copy()
+        rows = self._rows_in_force()
         fresh = env_param_rows(self.params, self.n_envs, env_params)
         for name in env_params:
             k = _lib.ENV_PARAM_NAMES.index(name)
@@ -336,10 +366,81 @@ class BatchedAviarySim:
         with torch.cuda.device(self.device):
             self._call("gpd_set_env_init", _dptr(x), _dptr(r))
 
+    def set_reset_pool(self, reset_pool):
+        """Install the pools an env draws its next drone and start pose from at each auto-reset
+        (``gpd_set_reset_pool``), or clear them with None.  ``reset_pool`` is a dict, every key
+        optional: ``env_params`` {name: array[P]} (names left out take the nominal drone, as
+        ``env_param_rows`` does), ``initial_xyzs`` / ``initial_rpys`` (Q, D, 3), ``seed``.  Without
+        ``env_params`` the parameters are never redrawn, without ``initial_xyzs`` the poses.  The
+        draw is :func:`reset_pool_draw` of (seed, stream, env, episode number); :meth:`reset` draws
+        nothing.  A synchronous upload.  What the old pools drew stays in force as the env's own row
+        and pose.  Replacing a pool by another of any size keeps a captured graph valid; turning
+        a pool on or off launches another kernel, so graphs captured before must be re-captured.
+        Checkpoints carry neither pools nor draws."""
+        self._need_het("set_reset_pool")
+        pool = dict(reset_pool or {})
+        unknown = set(pool) - {"env_params", "initial_xyzs", "initial_rpys", "seed"}
+        if unknown:
+            raise ValueError(f"unknown reset_pool keys {sorted(unknown)}")
+        ep = pool.get("env_params")
+        rows = np.empty((0, len(_lib.ENV_PARAM_NAMES)))
+        if ep is not None:
+            sizes = {np.size(v) for v in ep.values() if np.ndim(v) > 0}
+            if len(sizes) > 1:
+                raise ValueError(f"reset_pool env_params arrays differ in length: {sorted(sizes)}")
+            rows = env_param_rows(self.params, sizes.pop() if sizes else 1, ep)
+        poses = []
+        for name in ("initial_xyzs", "initial_rpys"):
+            a = pool.get(name)
+            if a is not None:
+                a = np.asarray(a, dtype=np.float64)
+                if a.ndim != 3 or a.shape[1:] != (self.drones_per_env, 3):
+                    raise ValueError(f"reset_pool {name} must have shape (Q, {self.drones_per_env}, 3), got {a.shape}")
+                a = np.ascontiguousarray(a)
+            poses.append(a)
+        x, r = poses
+        if r is not None and (x is None or r.shape != x.shape):
+            raise ValueError("reset_pool initial_rpys needs initial_xyzs of the same shape")
+        in_force = self._rows_in_force()
+        with torch.cuda.device(self.device):
+            self._call("gpd_set_reset_pool", _dptr(rows) if len(rows) else None, len(rows), _dptr(x), _dptr(r),
+                       0 if x is None else x.shape[0], int(pool.get("seed", 0)) & 0xffffffff)
+        self._env_rows, self._pool_rows = in_force, rows
+
+    def reset_draws(self):
+        """[E, 3] int32 on the device (``gpd_get_reset_draws``): each env's episode number (0 at
+        create, +1 at each auto-reset), parameter-pool row in force and pose-pool index in force;
+        -1 = not drawn (the env's create / set_env_params / set_initial_poses value)."""
+        self._need_het("reset_draws")
+        out = torch.empty((self.n_envs, 3), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._call("gpd_get_reset_draws", _ptr(out), _stream(self.device))
+        return out
+
+    def env_table(self):
+        """Diagnostic (``gpd_get_env_table``): the device's per-env constant table, [E, 18] float64
+        on the host."""
+        self._need_het("env_table")
+        out = np.empty((self.n_envs, 18), dtype=np.float64)
+        with torch.cuda.device(self.device):
+            self._call("gpd_get_env_table", _dptr(out))
+        return out
+
+    def _rows_in_force(self):
+        """[E, 11]: the pool row where an env's drawn row index is >= 0, its own row otherwise."""
+        if not self.het:
+            return env_param_rows(self.params, self.n_envs)
+        rows = self._env_rows.copy()
+        if len(self._pool_rows):
+            idx = self.reset_draws()[:, 1].cpu().numpy()
+            rows[idx >= 0] = self._pool_rows[idx[idx >= 0]]
+        return rows
+
     @property
     def env_params(self):
-        """The current per-env parameters as {name: array[E]} (every env nominal on a plain sim)."""
-        rows = self._env_rows if self.het else env_param_rows(self.params, self.n_envs)
+        """The per-env parameters in force as {name: array[E]} (every env nominal on a plain sim):
+        with a reset pool, the drawn pool row of the envs that have drawn one."""
+        rows = self._rows_in_force()
         return {name: rows[:, k].copy() for k, name in enumerate(_lib.ENV_PARAM_NAMES)}
 
     @property
@@ -347,8 +448,7 @@ class BatchedAviarySim:
         """Per-env derived constants (BaseAviary.py:117-128) from ``gpd_env_derive``: a dict of [E]
         float64 arrays (gravity, hover_rpm, max_rpm, max_thrust, max_xy_torque, max_z_torque,
         gnd_eff_h_clip)."""
-        rows = self._env_rows if self.het else env_param_rows(self.params, self.n_envs)
-        return env_derive(self.params, rows)
+        return env_derive(self.params, self._rows_in_force())
 
     def _field(self, name, dtype, shape):
         off, n = self.pack_layout[name]

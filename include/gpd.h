@@ -229,6 +229,47 @@ int gpd_set_env_init(gpd_sim* sim, const double* xyzs_host, const double* rpys_h
  * uses) in the last bit; a het sim's ground-effect clip height is this function's value. */
 int gpd_env_derive(const gpd_drone_params* base, const gpd_env_params* rows, int n, gpd_constants* out);
 
+/* ---- Reset pools: a new drone and a new start pose for each episode of a het sim, drawn on the
+ * device at auto-reset (domain randomisation as a fresh env object per episode; no host sync, no
+ * extra launch).
+ *
+ * Pools for auto-reset on a het sim (GPD_EINVAL on a plain sim).  All arguments are host memory
+ * and are copied.
+ *   rows_host [n_rows]                    n_rows == 0: parameters are never redrawn
+ *   xyzs_host / rpys_host [n_poses][D][3] n_poses == 0: poses are never redrawn; rpys NULL = zeros
+ * Both 0 clears the pool.  Rows and poses are validated as at create, before any device call (the
+ * message names the pool row or pool pose), and derived by the code that derives the het tables:
+ * a pool row's constants are bit-identical to what gpd_set_env_params would upload for that row,
+ * a pool pose's MultiHover targets are xyz + (0,0,1/(i+1)).
+ * When env e auto-resets for the k-th time (k = 1, 2, ...: its episode number), the step kernel
+ * gives it row gpd_reset_pool_draw of (seed, 1, e, k, n_rows) and pose gpd_reset_pool_draw of
+ * (seed, 2, e, k, n_poses), copies them into the env's tables and resets the env to the drawn pose.
+ * That step's reward, flags and terminal row are the old drone's.  gpd_reset draws nothing: an
+ * env goes back to the pose in force.  gpd_step_seq and graph replay work unchanged.
+ * Synchronous, like gpd_set_env_params.  What the old pools drew stays in force, as the env's own
+ * row and pose (index -1); the episode numbers stay.  Replacing one pool by another of any size
+ * keeps a captured graph valid.  Turning a pool on (from none) or off (both 0) changes which
+ * kernel gpd_step launches: graphs captured before that must be re-captured.
+ * gpd_set_env_params / gpd_set_env_init set the row / pose index back to -1 for every env.
+ * The checkpoint blob carries neither pools nor draws (as with the het tables); restoring them
+ * is out of scope. */
+int gpd_set_reset_pool(gpd_sim* sim, const gpd_env_params* rows_host, int n_rows, const double* xyzs_host,
+                       const double* rpys_host, int n_poses, unsigned seed);
+/* out_dev [E][3] int32, device: episode number, row index in force, pose index in force.  An
+ * index of -1 means "not drawn": the env's create / set_env_params / set_env_init value. */
+int gpd_get_reset_draws(gpd_sim* sim, int* out_dev, void* stream);
+/* Diagnostic: the device's per-env constant table as [E][18] doubles in host memory (m, gravity,
+ * 1/m, kf, km, arm, arm/sqrt(2), ixx, iyy, izz, 1/ixx, 1/iyy, 1/izz, float32(hover_rpm),
+ * gnd_eff_coeff, gnd_eff_h_clip, drag_coeff_xy, drag_coeff_z).  Synchronous. */
+int gpd_get_env_table(gpd_sim* sim, double* out_host);
+/* Host-only and pure: the pool draw.  All arithmetic is uint32; the last step is one 32x32 -> 64
+ * multiply:
+ *   mix32(x): x ^= x>>16; x *= 0x7feb352d; x ^= x>>15; x *= 0x846ca68b; x ^= x>>16
+ *   h = mix32(seed ^ (0x9e3779b9 * stream)); h = mix32(h + env); h = mix32(h + episode)
+ *   result = (uint64(h) * n) >> 32
+ * stream: 1 = parameter rows, 2 = poses.  n < 1 gives 0. */
+int gpd_reset_pool_draw(unsigned seed, int stream, long long env, int episode, int n);
+
 /* reset(): envs with env_mask[e] != 0 (env_mask == NULL: all envs) go back to INIT_XYZS /
  * INIT_RPYS with zero velocities, step_counter 0, last_clipped_action 0.  The action ring is
  * NOT cleared (the reference never clears action_buffer).  If obs != NULL the reset
