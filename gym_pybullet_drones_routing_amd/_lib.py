@@ -24,6 +24,9 @@ GPD_MODEL_CF2X, GPD_MODEL_CF2P, GPD_MODEL_RACE = 0, 1, 2
 GPD_ACT_RPM, GPD_ACT_ONE_D_RPM, GPD_ACT_PID, GPD_ACT_VEL, GPD_ACT_ONE_D_PID = 0, 1, 2, 3, 4
 GPD_ABI_VERSION = 7
 CTRL_COMPS = 9  # integral_pos_e(3) integral_rpy_e(3) last_rpy(3)
+# a gpd_set_pid_gains row: the six coefficient triples in gpd_pid_params' order
+PID_GAIN_FIELDS = ("p_coeff_for", "i_coeff_for", "d_coeff_for", "p_coeff_tor", "i_coeff_tor", "d_coeff_tor")
+PID_GAIN_COMPS = 18
 GPD_TASK_NONE, GPD_TASK_HOVER, GPD_TASK_MULTIHOVER = 0, 1, 2
 GPD_F_GND, GPD_F_DRAG, GPD_F_DW, GPD_F_GEOM_WRENCH, GPD_F_BULLET, GPD_F_NO_PLANE = 1, 2, 4, 8, 16, 32
 GPD_F_NO_DRONE_CONTACT = 64
@@ -35,7 +38,8 @@ EXPORTED = ("gpd_abi_version", "gpd_last_error", "gpd_default_params", "gpd_crea
             "gpd_get_constants", "gpd_reset", "gpd_step", "gpd_step_seq", "gpd_integrate", "gpd_get_state20",
             "gpd_get_raw_state", "gpd_set_raw_state", "gpd_get_step_counters",
             "gpd_set_step_counters", "gpd_state_bytes", "gpd_save_state", "gpd_load_state",
-            "gpd_default_pid_params", "gpd_set_pid_params", "gpd_get_ctrl_state", "gpd_set_ctrl_state",
+            "gpd_default_pid_params", "gpd_set_pid_params", "gpd_set_pid_gains", "gpd_get_pid_gains",
+            "gpd_get_ctrl_state", "gpd_set_ctrl_state",
             "gpd_nonfinite", "gpd_cmd_step", "gpd_cmd_rollout", "gpd_adjacency", "gpd_pack_layout_of", "gpd_handoff_pack",
             "gpd_handoff_unpack",
             "gpd_create_het", "gpd_set_env_params", "gpd_set_env_init", "gpd_env_derive",
@@ -139,6 +143,8 @@ def load():
         "gpd_load_state": (ci, [vp, vp, vp]),
         "gpd_default_pid_params": (ci, [ctypes.POINTER(PidParams)]),
         "gpd_set_pid_params": (ci, [vp, ctypes.POINTER(PidParams)]),
+        "gpd_set_pid_gains": (ci, [vp, vp]),
+        "gpd_get_pid_gains": (ci, [vp, vp]),
         "gpd_get_ctrl_state": (ci, [vp, vp, vp]),
         "gpd_set_ctrl_state": (ci, [vp, vp, vp]),
         "gpd_nonfinite": (ci, [vp, vp, vp]),

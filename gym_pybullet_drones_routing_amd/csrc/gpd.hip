@@ -152,6 +152,10 @@ struct gpd_sim {
   void* d_pool_target = nullptr;  // [Q][D][3]
   std::vector<gpd_env_params> pool_rows;    // [P] host copies: fold_draws makes a drawn row / pose
   std::vector<double> pool_xyz, pool_rpy;   // [Q][D][3] the env's own before the pool is replaced
+  // per-drone controller gains (gpd_set_pid_gains; the PG instantiations of the command step kernels)
+  void* d_gains = nullptr;        // tiled [npad/64][18][64], allocated at the first install, freed at destroy
+  bool gains_on = false;          // a table is in force: the controller modes launch the _pg kernels
+  std::vector<double> gains;      // [N][18] the table's values as stored (rounded to the sim's real type)
 };
 
 namespace {
@@ -566,6 +570,19 @@ template <typename R, int MAXT>
 const void* cmd_step_wide_fn(bool ctrl) {
   return ctrl ? (const void*)cmd_step_kernel_wide<R, MAXT, true> : (const void*)cmd_step_kernel_wide<R, MAXT, false>;
 }
+// The controller modes while a per-drone gain table is in force (gpd_set_pid_gains): the same
+// controller instantiations with PG, which read the kernels' last argument.
+template <typename R>
+const void* cmd_step_pg_fn(bool multi) {
+  return multi ? (const void*)cmd_step_kernel<R, true, kPfRuntime, true, true>
+               : (const void*)cmd_step_kernel<R, false, kPfRuntime, true, true>;
+}
+template <typename R>
+const void* cmd_step_wide_pg_fn(int D) {
+  return D <= 256 ? (const void*)cmd_step_kernel_wide<R, 256, true, true>
+                  : (D <= 512 ? (const void*)cmd_step_kernel_wide<R, 512, true, true>
+                              : (const void*)cmd_step_kernel_wide<R, 1024, true, true>);
+}
 
 template <typename R>
 int launch_cmd_step(gpd_sim* s, int mode, const void* actions, void* obs20, hipStream_t st) {
@@ -576,14 +593,17 @@ int launch_cmd_step(gpd_sim* s, int mode, const void* actions, void* obs20, hipS
   const bool ctrl = mode != GPD_CMD_RPM;
   R max_rpm = (R)s->K.max_rpm;
   R* o = (R*)obs20;
-  void* args[] = {(void*)&v, (void*)&c, (void*)&actions, (void*)&mode, (void*)&max_rpm, (void*)&o};
+  const bool pg = ctrl && s->gains_on;
+  const R* g = pg ? (const R*)s->d_gains : nullptr;   // read by the PG instantiations only
+  void* args[] = {(void*)&v, (void*)&c, (void*)&actions, (void*)&mode, (void*)&max_rpm, (void*)&o, (void*)&g};
   if (s->D > kWave) {
-    const void* fw = s->D <= 256 ? cmd_step_wide_fn<R, 256>(ctrl)
+    const void* fw = pg ? cmd_step_wide_pg_fn<R>(s->D)
+                     : s->D <= 256 ? cmd_step_wide_fn<R, 256>(ctrl)
                      : (s->D <= 512 ? cmd_step_wide_fn<R, 512>(ctrl) : cmd_step_wide_fn<R, 1024>(ctrl));
     HIP_TRY(hipLaunchKernel(fw, dim3(s->E), dim3((s->D + kWave - 1) / kWave * kWave), args, 0, st));
     return GPD_OK;
   }
-  const void* f = cmd_step_fn<R>(s->D > 1, s->cfg.physics_flags == 0, ctrl);
+  const void* f = pg ? cmd_step_pg_fn<R>(s->D > 1) : cmd_step_fn<R>(s->D > 1, s->cfg.physics_flags == 0, ctrl);
   HIP_TRY(hipLaunchKernel(f, dim3(grid_for(s->N, s->tpb)), dim3(kWave), args, 0, st));
   return GPD_OK;
 }
@@ -633,7 +653,11 @@ int launch_cmd_rollout(gpd_sim* s, int mode, const void* actions, int n_steps, i
   }
   const SimView<R> v = make_view<R>(s);
   const Consts<R>* c = (const Consts<R>*)s->d_consts;
-  const void* f = cmd_rollout_fn<R>(s->D > 1, s->cfg.physics_flags == 0, mode != GPD_CMD_RPM);
+  const bool pg = mode != GPD_CMD_RPM && s->gains_on;
+  const void* f = pg ? (s->D > 1 ? (const void*)cmd_rollout_kernel<R, true, kPfRuntime, true, true>
+                                 : (const void*)cmd_rollout_kernel<R, false, kPfRuntime, true, true>)
+                     : cmd_rollout_fn<R>(s->D > 1, s->cfg.physics_flags == 0, mode != GPD_CMD_RPM);
+  const R* g = pg ? (const R*)s->d_gains : nullptr;   // read by the PG instantiations only
   R max_rpm = (R)s->K.max_rpm;
   for (int t0 = 0; t0 < n_steps; t0 += chunk) {
     int n = n_steps - t0 < chunk ? n_steps - t0 : chunk;
@@ -642,7 +666,7 @@ int launch_cmd_rollout(gpd_sim* s, int mode, const void* actions, int n_steps, i
     long long rec_row = t0 / record_every;
     R* o = t0 + n == n_steps ? (R*)obs20 : nullptr;
     void* args[] = {(void*)&v, (void*)&c, (void*)&a, (void*)&mode, (void*)&max_rpm, (void*)&n, (void*)&record_every,
-                    (void*)&rec_phase, (void*)&rec_row, (void*)&tr, (void*)&o, (void*)&m, (void*)&carry};
+                    (void*)&rec_phase, (void*)&rec_row, (void*)&tr, (void*)&o, (void*)&m, (void*)&carry, (void*)&g};
     HIP_TRY(hipLaunchKernel(f, dim3(grid_for(s->N, s->tpb)), dim3(kWave), args, 0, st));
   }
   return GPD_OK;
@@ -713,6 +737,7 @@ void free_sim(gpd_sim* s) {
   if (s->d_pool_target) (void)hipFree(s->d_pool_target);
   if (s->d_dc_tab) (void)hipFree(s->d_dc_tab);
   if (s->d_dc_rows) (void)hipFree(s->d_dc_rows);
+  if (s->d_gains) (void)hipFree(s->d_gains);
   delete s;
 }
 
@@ -1426,6 +1451,9 @@ int gpd_step(gpd_sim* sim, const float* actions, float* obs, float* reward, uint
   if (sim->A == 4 && !aligned16(actions)) return fail(GPD_EINVAL, "gpd_step: actions must be 16-byte aligned");
   if (sim->A == 4 && (!aligned16(obs) || (terminal_obs && !aligned16(terminal_obs))))
     return fail(GPD_EINVAL, "gpd_step: obs buffers must be 16-byte aligned");
+  if (sim->gains_on)
+    return fail(GPD_EUNSUPPORTED, "gpd_step: a per-drone gain table is in force (gpd_set_pid_gains) and the RL step "
+                                  "reads the sim-wide coefficients; clear the table with gpd_set_pid_gains(sim, NULL)");
   hipStream_t st = (hipStream_t)stream;
   return sim->prec == GPD_F64
              ? launch_step<double>(sim, actions, obs, reward, terminated, truncated, terminal_obs, st)
@@ -1440,6 +1468,9 @@ int gpd_step_seq(gpd_sim* sim, const float* actions, int n_slots, int n_steps, f
   if (sim->A == 4 && !aligned16(actions)) return fail(GPD_EINVAL, "gpd_step_seq: actions must be 16-byte aligned");
   if (sim->A == 4 && (!aligned16(obs) || (terminal_obs && !aligned16(terminal_obs))))
     return fail(GPD_EINVAL, "gpd_step_seq: obs buffers must be 16-byte aligned");
+  if (sim->gains_on)
+    return fail(GPD_EUNSUPPORTED, "gpd_step_seq: a per-drone gain table is in force (gpd_set_pid_gains) and the RL step "
+                                  "reads the sim-wide coefficients; clear the table with gpd_set_pid_gains(sim, NULL)");
   hipStream_t st = (hipStream_t)stream;
   const size_t slot = (size_t)sim->N * sim->A;
   for (int t = 0; t < n_steps; ++t) {
@@ -1574,6 +1605,76 @@ int gpd_set_pid_params(gpd_sim* sim, const gpd_pid_params* params) {
   sim->pid = *params;
   HIP_TRY(hipDeviceSynchronize());
   return sim->prec == GPD_F64 ? upload_tables<double>(sim) : upload_tables<float>(sim);
+}
+
+int gpd_set_pid_gains(gpd_sim* sim, const double* gains) {
+  if (!sim) return fail(GPD_EINVAL, "gpd_set_pid_gains: NULL sim");
+  if (!act_is_pid(sim->cfg.act_type))
+    return fail(GPD_EINVAL, "gpd_set_pid_gains: the sim's action type has no controller");
+  if (!gains) {   // the sim-wide coefficients are back in force; the buffer and its address stay
+    sim->gains_on = false;
+    return GPD_OK;
+  }
+  const size_t N = (size_t)sim->N;
+  for (size_t n = 0; n < N; ++n)
+    for (int k = 0; k < kGainComps; ++k)
+      if (!std::isfinite(gains[n * kGainComps + k]))
+        return fail(GPD_EINVAL, "gpd_set_pid_gains: non-finite value in row " + std::to_string(n) + ", column " +
+                                    std::to_string(k));
+  // rounded once to the sim's real type, tiled [npad/64][18][64] (padding drones: zeros, never read)
+  const bool f64 = sim->prec == GPD_F64;
+  const size_t count = (size_t)kGainComps * (size_t)sim->npad;
+  std::vector<double> stored(N * kGainComps);
+  std::vector<double> t64(f64 ? count : 0, 0.0);
+  std::vector<float> t32(f64 ? 0 : count, 0.0f);
+  for (size_t n = 0; n < N; ++n)
+    for (int k = 0; k < kGainComps; ++k) {
+      const double x = gains[n * kGainComps + k];
+      const size_t at = (size_t)tidx((long long)n, k, kGainComps);
+      if (f64) {
+        t64[at] = x;
+        stored[n * kGainComps + k] = x;
+      } else {
+        t32[at] = (float)x;
+        stored[n * kGainComps + k] = (double)t32[at];
+      }
+    }
+  if (!f64)   // a finite double past float's range rounds to infinity
+    for (size_t i = 0; i < stored.size(); ++i)
+      if (!std::isfinite(stored[i]))
+        return fail(GPD_EINVAL, "gpd_set_pid_gains: non-finite value in row " + std::to_string(i / kGainComps) +
+                                    ", column " + std::to_string(i % kGainComps) + " (out of float32 range)");
+  const size_t bytes = count * (f64 ? sizeof(double) : sizeof(float));
+  HIP_TRY(hipDeviceSynchronize());
+  if (!sim->d_gains && hipMalloc(&sim->d_gains, bytes) != hipSuccess) {
+    sim->d_gains = nullptr;
+    return fail(GPD_ENOMEM, "gpd_set_pid_gains: device allocation of the gain table failed");
+  }
+  HIP_TRY(hipMemcpy(sim->d_gains, f64 ? (const void*)t64.data() : (const void*)t32.data(), bytes, hipMemcpyHostToDevice));
+  sim->gains.swap(stored);
+  sim->gains_on = true;
+  return GPD_OK;
+}
+
+int gpd_get_pid_gains(gpd_sim* sim, double* out) {
+  if (!sim || !out) return fail(GPD_EINVAL, "gpd_get_pid_gains: NULL argument");
+  if (!act_is_pid(sim->cfg.act_type))
+    return fail(GPD_EINVAL, "gpd_get_pid_gains: the sim's action type has no controller");
+  const size_t N = (size_t)sim->N;
+  if (sim->gains_on) {
+    std::memcpy(out, sim->gains.data(), N * kGainComps * sizeof(double));
+    return GPD_OK;
+  }
+  // no table: the sim-wide triples as the kernels read them (rounded to the sim's real type)
+  const gpd_pid_params& Q = sim->pid;
+  const double* tri[6] = {Q.p_coeff_for, Q.i_coeff_for, Q.d_coeff_for, Q.p_coeff_tor, Q.i_coeff_tor, Q.d_coeff_tor};
+  double row[kGainComps];
+  for (int k = 0; k < kGainComps; ++k) {
+    const double x = tri[k / 3][k % 3];
+    row[k] = sim->prec == GPD_F64 ? x : (double)(float)x;
+  }
+  for (size_t n = 0; n < N; ++n) std::memcpy(out + n * kGainComps, row, sizeof(row));
+  return GPD_OK;
 }
 
 int gpd_get_ctrl_state(gpd_sim* sim, void* out, void* stream) {

@@ -50,29 +50,31 @@ __device__ __forceinline__ void cmd_row_load(const void* __restrict__ actions, i
 // command's targets: from the row in registers (cmd_row_to_rpm) or straight from memory
 // (cmd_to_rpm; a single step has no row to prefetch, and holding the 7 reals across the mode
 // branch spills in the f64 kernels).
+// k: the constants the controller runs on: Consts::pid, or the lane's own copy of it with its
+// drone's gain row (pid_with_gains).
 template <typename R, typename F>
-__device__ __forceinline__ void cmd_ctrl_rpm(const Consts<R>& c, const Drone<R>& s, R cs[9], R rpm[4], F&& targets) {
+__device__ __forceinline__ void cmd_ctrl_rpm(const PidConsts<R>& k, const Drone<R>& s, R cs[9], R rpm[4], F&& targets) {
   R qn[4], Rm[9], rpy[3];
   readback_fused(s.qx, s.qy, s.qz, s.qw, qn, Rm);
   quat_to_euler(qn, rpy[0], rpy[1], rpy[2]);
   const R pos[3] = {s.px, s.py, s.pz}, vel[3] = {s.vx, s.vy, s.vz};
   R tpos[3], tvel[3], tyaw;
   targets(pos, rpy, tpos, tyaw, tvel);
-  dsl_pid<R, false>(c.pid, pos, Rm, rpy, vel, tpos, tyaw, tvel, cs, rpm);
+  dsl_pid<R, false>(k, pos, Rm, rpy, vel, tpos, tyaw, tvel, cs, rpm);
 }
 
 // The row in registers -> RPMs.
 template <typename R, bool CTRL>
-__device__ __forceinline__ void cmd_row_to_rpm(const Consts<R>& c, int mode, const R a[cmd_row_regs<CTRL>()], R max_rpm,
+__device__ __forceinline__ void cmd_row_to_rpm(const PidConsts<R>& k, int mode, const R a[cmd_row_regs<CTRL>()], R max_rpm,
                                                const Drone<R>& s, R cs[9], R rpm[4]) {
   if (!CTRL) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) rpm[k] = np_clip(a[k], R(0), max_rpm);
   } else {
-    cmd_ctrl_rpm(c, s, cs, rpm, [&](const R pos[3], const R rpy[3], R tpos[3], R& tyaw, R tvel[3]) {
+    cmd_ctrl_rpm(k, s, cs, rpm, [&](const R pos[3], const R rpy[3], R tpos[3], R& tyaw, R tvel[3]) {
       if (mode == CMD_VEL) {
         const float af[4] = {(float)a[0], (float)a[1], (float)a[2], (float)a[3]};
-        pid_targets<R, ACT_VEL>(c.pid, af, pos, rpy, tpos, tyaw, tvel);
+        pid_targets<R, ACT_VEL>(k, af, pos, rpy, tpos, tyaw, tvel);
       } else {
         tpos[0] = a[0]; tpos[1] = a[1]; tpos[2] = a[2];
         tyaw = a[3];
@@ -84,18 +86,18 @@ __device__ __forceinline__ void cmd_row_to_rpm(const Consts<R>& c, int mode, con
 
 // Drone n's command of a single step -> RPMs.
 template <typename R, bool CTRL>
-__device__ __forceinline__ void cmd_to_rpm(const Consts<R>& c, int mode, const void* __restrict__ actions, long long n,
+__device__ __forceinline__ void cmd_to_rpm(const PidConsts<R>& k, int mode, const void* __restrict__ actions, long long n,
                                            R max_rpm, const Drone<R>& s, R cs[9], R rpm[4]) {
   if (!CTRL) {
     R a[4];
     cmd_row_load<R, false>(actions, mode, n, a);
-    cmd_row_to_rpm<R, false>(c, mode, a, max_rpm, s, cs, rpm);
+    cmd_row_to_rpm<R, false>(k, mode, a, max_rpm, s, cs, rpm);
   } else {
-    cmd_ctrl_rpm(c, s, cs, rpm, [&](const R pos[3], const R rpy[3], R tpos[3], R& tyaw, R tvel[3]) {
+    cmd_ctrl_rpm(k, s, cs, rpm, [&](const R pos[3], const R rpy[3], R tpos[3], R& tyaw, R tvel[3]) {
       if (mode == CMD_VEL) {
         float a[4];
         load_rpm4((const float*)actions + n * 4, a);
-        pid_targets<R, ACT_VEL>(c.pid, a, pos, rpy, tpos, tyaw, tvel);
+        pid_targets<R, ACT_VEL>(k, a, pos, rpy, tpos, tyaw, tvel);
       } else {
         const R* w = (const R*)actions + n * 7;
         tpos[0] = w[0]; tpos[1] = w[1]; tpos[2] = w[2];
@@ -151,13 +153,73 @@ __device__ __forceinline__ void unmark_last_in_ring(const SimView<R>& v, long lo
 }
 
 // ---------------------------------------------------------------------------------------
+// Per-drone controller gains (gpd_set_pid_gains).  The table is tiled like v.ctrl,
+// [npad/64][18][64] reals: column k of drone n at tidx(n, k, 18), so a wave's load of one column
+// is one contiguous 64-real line.  A row is gpd_pid_params' six triples in its order:
+// P/I/D_COEFF_FOR, P/I/D_COEFF_TOR.
+constexpr int kGainComps = 18;
+
+// Drone n's row into registers: issued beside the loads of its state and controller state.
+template <typename R>
+__device__ __forceinline__ void pid_gains_load(const R* __restrict__ gains, long long n, R g[kGainComps]) {
+#pragma unroll
+  for (int k = 0; k < kGainComps; ++k) g[k] = gains[tidx(n, k, kGainComps)];
+}
+
+// The lane's own controller constants: the sim-wide block with the six triples replaced by the
+// drone's row.  Everything else (PWM constants, mixer, gravity, kf, ctrl_dt, speed_limit) stays
+// wave-uniform.
+template <typename R>
+__device__ __forceinline__ PidConsts<R> pid_with_gains(const PidConsts<R>& base, const R g[kGainComps]) {
+  PidConsts<R> k = base;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    k.p_for[i] = g[i];     k.i_for[i] = g[3 + i];  k.d_for[i] = g[6 + i];
+    k.p_tor[i] = g[9 + i]; k.i_tor[i] = g[12 + i]; k.d_tor[i] = g[15 + i];
+  }
+  return k;
+}
+
+// The one-wave kernels keep the lane's constants in an LDS slot of its own and hand the controller
+// a reference to it: dsl_pid then reads its constants through a pointer to a PidConsts, the form in
+// which the no-table instantiation reads Consts::pid, and 18 reals per lane stay out of the
+// registers across the rollout's step loop.  The slot is read back under the lane id from mbcnt,
+// which equals tid in these one-wave blocks but which the compiler does not know to: it does not
+// forward the stored values into the controller, and (unlike an asm statement) the index is no
+// scheduling boundary, so the loads that follow issue ahead of the staging's waits.  8 bytes of
+// padding: the slots' stride is 78 (f64) / 42 (f32) dwords, two lanes per bank at worst.
+// The whole PidConsts is staged, its wave-uniform part (19 reals + the speed limit) 64 times: 15 KB
+// of the 19.5 KB (f64) are copies, loaded by every lane from one address.  A shared copy of that
+// part would need the controller to read two structs, a form the no-table kernel does not have.
+// COMPILER DEPENDENCE: that a table of the sim-wide gains is bit-identical to no table
+// (tests/test_gpu_pid_gains.py) rests on this form and on where the kernels call it, i.e. on how
+// the hipcc it was developed with orders operands before it contracts a*b + c*d in the Bullet code,
+// which is compiled with contraction left to it.  Another compiler may break that test without any
+// change here; the robust remedy is explicit contraction in that shared code.
+template <typename R>
+struct LanePid {
+  PidConsts<R> k;
+  R pad[8 / sizeof(R)];
+};
+template <typename R>
+__device__ __forceinline__ const PidConsts<R>& pid_stage_lane(LanePid<R>* tile, int tid, const PidConsts<R>& base,
+                                                              const R g[kGainComps]) {
+  tile[tid].k = pid_with_gains(base, g);
+  const int slot = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));   // == tid (one-wave blocks)
+  return tile[slot].k;
+}
+
+// ---------------------------------------------------------------------------------------
 // gpd_cmd_step for envs of up to 64 drones: one wave per block, the geometry of integrate_kernel
 // (whole envs per block, v.tpb drones), one control step as step_kernel runs it.
 // PF: 0 (plain DYN) or kPfRuntime; CTRL: the instantiation runs the controller (VEL / WAYPOINT).
-template <typename R, bool MULTI, int PF, bool CTRL>
+// PG: a per-drone gain table is in force and the controller runs on the drone's own row of `gains`;
+// else on Consts::pid, and `gains` (the last kernel argument, null) is never read.
+template <typename R, bool MULTI, int PF, bool CTRL, bool PG = false>
 __global__ __launch_bounds__(kWave) void cmd_step_kernel(SimView<R> v, const Consts<R>* __restrict__ cp,
                                                          const void* __restrict__ actions, int mode, R max_rpm,
-                                                         R* __restrict__ obs20) {
+                                                         R* __restrict__ obs20, const R* __restrict__ gains) {
+  static_assert(CTRL || !PG, "the gain table is read by the controller modes only");
   __shared__ R sx[MULTI ? 2 * kWave : 1], sy[MULTI ? 2 * kWave : 1], sz[MULTI ? 2 * kWave : 1];
   __shared__ R rows[20 * kPad];   // the block's state20 rows, column-major (rows20_copy_out)
   const Consts<R>& c = *cp;
@@ -171,6 +233,24 @@ __global__ __launch_bounds__(kWave) void cmd_step_kernel(SimView<R> v, const Con
   const int nact = (int)(nleft < v.tpb ? nleft : v.tpb);   // drones owned by this block
   const bool active = tid < nact;
   const long long nn = active ? n : n0;   // inactive lanes: the block's first drone (step_kernel)
+  // PG: the row's loads, the controller state's and the staging stand ahead of every load the no-table
+  // kernel has: what follows is then that kernel's code in that kernel's order, and the compiler's
+  // choices in it (which product of a sum it contracts) stay the same.  As compiled:
+  // on single-drone envs the state's 13 loads, next in the block, issue in the same batch, ahead of
+  // the staging's waits (one round trip; the four last_clipped_action loads of a sim with drag sit
+  // behind a branch and issue after them).  On multi-drone envs the pair-table code (branches
+  // and dependent loads of its own, in the no-table kernel too) stands between the staging and the
+  // state's loads: there the staging's round trip comes on top of those the no-table kernel has.
+  const PidConsts<R>* pk = nullptr;
+  R cs_pg[PG ? 9 : 1];
+  if constexpr (PG) {
+    __shared__ LanePid<R> lane_pid[kWave];
+    R g[kGainComps];
+    pid_gains_load(gains, nn, g);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) cs_pg[k] = v.ctrl[tidx(nn, k, 9)];
+    pk = &pid_stage_lane(lane_pid, tid, c.pid, g);
+  }
   const bool drag = pf_on<PF>(c.flags, F_DRAG);
   const DcPairs dcp = dc_enabled<MULTI, PF>(c.flags) ? dc_pairs_for(v, tid, nact) : dc_pairs_none();
   Drone<R> s;
@@ -179,11 +259,18 @@ __global__ __launch_bounds__(kWave) void cmd_step_kernel(SimView<R> v, const Con
   DynK<R> dk = dyn_consts(c);
   R rpm[4];
   R cs[9];
-  if (CTRL) {
+  if constexpr (PG) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) cs[k] = cs_pg[k];
+  } else if (CTRL) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) cs[k] = v.ctrl[tidx(nn, k, 9)];
   }
-  cmd_to_rpm<R, CTRL>(c, mode, actions, nn, max_rpm, s, cs, rpm);
+  if constexpr (PG) {
+    cmd_to_rpm<R, CTRL>(*pk, mode, actions, nn, max_rpm, s, cs, rpm);
+  } else {
+    cmd_to_rpm<R, CTRL>(c.pid, mode, actions, nn, max_rpm, s, cs, rpm);
+  }
   // the same RPMs and wrench drive every substep
   R W[4];
   rpm_wrench<R, PF>(rpm, dk, c, W);
@@ -203,11 +290,12 @@ __global__ __launch_bounds__(kWave) void cmd_step_kernel(SimView<R> v, const Con
 }
 
 // gpd_cmd_step for envs of 65 .. 1024 drones: one env per workgroup of ceil(D / 64) waves
-// (integrate_kernel_wide), rows stored per lane.
-template <typename R, int MAXT, bool CTRL>
+// (integrate_kernel_wide), rows stored per lane.  PG and gains as cmd_step_kernel's.
+template <typename R, int MAXT, bool CTRL, bool PG = false>
 __global__ __launch_bounds__(MAXT) void cmd_step_kernel_wide(SimView<R> v, const Consts<R>* __restrict__ cp,
                                                              const void* __restrict__ actions, int mode, R max_rpm,
-                                                             R* __restrict__ obs20) {
+                                                             R* __restrict__ obs20, const R* __restrict__ gains) {
+  static_assert(CTRL || !PG, "the gain table is read by the controller modes only");
   __shared__ R sx[MAXT], sy[MAXT], sz[MAXT];
   const Consts<R>& c = *cp;
   const int D = v.D;
@@ -225,7 +313,14 @@ __global__ __launch_bounds__(MAXT) void cmd_step_kernel_wide(SimView<R> v, const
 #pragma unroll
     for (int k = 0; k < 9; ++k) cs[k] = v.ctrl[tidx(n, k, 9)];
   }
-  cmd_to_rpm<R, CTRL>(c, mode, actions, n, max_rpm, s, cs, rpm);
+  if constexpr (PG) {
+    R g[kGainComps];
+    pid_gains_load(gains, n, g);
+    const PidConsts<R> pk = pid_with_gains(c.pid, g);
+    cmd_to_rpm<R, CTRL>(pk, mode, actions, n, max_rpm, s, cs, rpm);
+  } else {
+    cmd_to_rpm<R, CTRL>(c.pid, mode, actions, n, max_rpm, s, cs, rpm);
+  }
   R W[4];
   rpm_wrench<R, kPfRuntime>(rpm, dk, c, W);
   for (int it = 0; it < dk.nsub; ++it) {

@@ -38,12 +38,18 @@ __device__ __forceinline__ void track_accumulate(R px, R py, R pz, R tx, R ty, R
 //   obs20      the rows after the launch's last step (null on all but a flight's last launch)
 //   metrics    [N][2] tracking sum / max over the WAYPOINT targets (null: none); carry != 0
 //              continues the values there, else the flight starts at zero
-template <typename R, bool MULTI, int PF, bool CTRL>
+//   gains      PG: the per-drone gain table (gpd_step_cmd.h); a lane loads its drone's row once per
+//              launch, in the batch of its state loads, and stages its controller constants in its
+//              LDS slot (pid_stage_lane), where the controller reads them on every step of the launch
+//              (PG as cmd_step_kernel's; else null and never read)
+template <typename R, bool MULTI, int PF, bool CTRL, bool PG = false>
 __global__ __launch_bounds__(kWave) void cmd_rollout_kernel(SimView<R> v, const Consts<R>* __restrict__ cp,
                                                             const void* __restrict__ actions, int mode, R max_rpm,
                                                             int n_steps, int rec_every, int rec_phase,
                                                             long long rec_row, R* __restrict__ traj,
-                                                            R* __restrict__ obs20, R* __restrict__ metrics, int carry) {
+                                                            R* __restrict__ obs20, R* __restrict__ metrics, int carry,
+                                                            const R* __restrict__ gains) {
+  static_assert(CTRL || !PG, "the gain table is read by the controller modes only");
   constexpr int CW = cmd_row_regs<CTRL>();
   __shared__ R sx[MULTI ? 2 * kWave : 1], sy[MULTI ? 2 * kWave : 1], sz[MULTI ? 2 * kWave : 1];
   __shared__ R rows[20 * kPad];   // the block's state20 rows, column-major (rows20_copy_out)
@@ -59,6 +65,16 @@ __global__ __launch_bounds__(kWave) void cmd_rollout_kernel(SimView<R> v, const 
   const int nact = (int)(nleft < v.tpb ? nleft : v.tpb);   // drones owned by this block
   const bool active = tid < nact;
   const long long nn = active ? n : n0;   // inactive lanes: the block's first drone (step_kernel)
+  // PG: the lane's controller constants for the whole launch, staged ahead of every load the
+  // no-table kernel has (cmd_step_kernel).  The controller state, the command row and the carried
+  // metrics load behind the staging's waits here: once per launch, not once per step.
+  const PidConsts<R>* pk = nullptr;
+  if constexpr (PG) {
+    __shared__ LanePid<R> lane_pid[kWave];
+    R g[kGainComps];
+    pid_gains_load(gains, nn, g);
+    pk = &pid_stage_lane(lane_pid, tid, c.pid, g);
+  }
   const bool drag = pf_on<PF>(c.flags, F_DRAG);
   const DcPairs dcp = dc_enabled<MULTI, PF>(c.flags) ? dc_pairs_for(v, tid, nact) : dc_pairs_none();
   Drone<R> s;
@@ -84,7 +100,8 @@ __global__ __launch_bounds__(kWave) void cmd_rollout_kernel(SimView<R> v, const 
     // the next step's row is in flight while this step's substeps run
     if (t + 1 < n_steps) cmd_row_load<R, CTRL>(actions, mode, (long long)(t + 1) * N + nn, nxt);
     R rpm[4];
-    cmd_row_to_rpm<R, CTRL>(c, mode, cur, max_rpm, s, cs, rpm);
+    if constexpr (PG) cmd_row_to_rpm<R, CTRL>(*pk, mode, cur, max_rpm, s, cs, rpm);
+    else cmd_row_to_rpm<R, CTRL>(c.pid, mode, cur, max_rpm, s, cs, rpm);
     // the same RPMs and wrench drive every substep; the drag of substep 1 sees the previous step's
     // RPMs (BaseAviary.py:359-372), here handed over in `last`
     R W[4];

@@ -130,6 +130,13 @@ class BaseRLAviary:
         """BaseControl.setPIDCoefficients on every drone's DSLPIDControl (PID action types)."""
         self.sim.set_pid_coefficients(**coeffs)
 
+    def set_pid_gains(self, **coeffs):
+        """Each drone's own DSLPIDControl coefficients (``BatchedAviarySim.set_pid_gains``; the keywords
+        of setPIDCoefficients, each (3,) or (1, NUM_DRONES, 3)).  CtrlAviary.step_to and VelocityAviary
+        fly on them; an RL env's step() is refused while they are in force (the RL step reads the
+        sim-wide coefficients): call ``self.sim.clear_pid_gains()`` to go back."""
+        self.sim.set_pid_gains(**coeffs)
+
     def getDroneIds(self):
         return np.arange(self.NUM_DRONES)
 

@@ -160,6 +160,51 @@ def _dptr(a):
     return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
 
 
+# set_pid_coefficients' keywords, in the order of a gain row's six triples (_lib.PID_GAIN_FIELDS)
+PID_GAIN_KEYWORDS = ("p_coeff_pos", "i_coeff_pos", "d_coeff_pos", "p_coeff_att", "i_coeff_att", "d_coeff_att")
+
+
+def pid_gain_rows(n_envs, drones_per_env, base, **coeffs):
+    """``gpd_set_pid_gains`` rows [N, 18] float64 (N = ``n_envs * drones_per_env``; a row is the six
+    coefficient triples in ``gpd_pid_params``' order).  ``base`` is a ``_lib.PidParams`` (its six
+    triples for every drone) or an [N, 18] array.  Each keyword of ``set_pid_coefficients``
+    (``p_coeff_pos`` ... ``d_coeff_att``) replaces its triple: shape (3,), (E, 3), (E, 1, 3) or
+    (E, D, 3); ``None`` keeps the base.  Any other shape, and any non-finite value, is a ValueError."""
+    E, D = int(n_envs), int(drones_per_env)
+    if E < 1 or D < 1:
+        raise ValueError(f"n_envs and drones_per_env must be >= 1, got {n_envs}, {drones_per_env}")
+    unknown = set(coeffs) - set(PID_GAIN_KEYWORDS)
+    if unknown:
+        raise ValueError(f"unknown coefficient names {sorted(unknown)}; expected a subset of {list(PID_GAIN_KEYWORDS)}")
+    rows = np.empty((E, D, 6, 3), dtype=np.float64)
+    if isinstance(base, _lib.PidParams):
+        for k, field in enumerate(_lib.PID_GAIN_FIELDS):
+            rows[:, :, k, :] = np.array(list(getattr(base, field)), dtype=np.float64)
+    else:
+        b = np.asarray(base, dtype=np.float64)
+        if b.shape != (E * D, _lib.PID_GAIN_COMPS):
+            raise ValueError(f"base must be a PidParams or an array of shape {(E * D, _lib.PID_GAIN_COMPS)}, "
+                             f"got shape {b.shape}")
+        rows[:] = b.reshape(E, D, 6, 3)
+    for k, name in enumerate(PID_GAIN_KEYWORDS):
+        val = coeffs.get(name)
+        if val is None:
+            continue
+        v = np.asarray(val, dtype=np.float64)
+        if v.shape == (3,):
+            v = v.reshape(1, 1, 3)
+        elif v.shape == (E, 3):
+            v = v.reshape(E, 1, 3)
+        elif v.shape not in ((E, 1, 3), (E, D, 3)):
+            raise ValueError(f"{name} must have shape (3,), ({E}, 3), ({E}, 1, 3) or ({E}, {D}, 3), got {v.shape}")
+        rows[:, :, k, :] = v
+    rows = np.ascontiguousarray(rows.reshape(E * D, _lib.PID_GAIN_COMPS))
+    if not np.isfinite(rows).all():
+        n, c = np.argwhere(~np.isfinite(rows))[0]
+        raise ValueError(f"non-finite gain in row {n}, column {c}")
+    return rows
+
+
 _DERIVED = ("gravity", "hover_rpm", "max_rpm", "max_thrust", "max_xy_torque", "max_z_torque", "gnd_eff_h_clip")
 
 
@@ -499,7 +544,7 @@ class BatchedAviarySim:
             with torch.cuda.device(self.device):
                 rc = self._step_fn(self._h, a.data_ptr(), *self._out_ptrs, tptr, _stream(self.device))
         if rc != 0:
-            _lib.check("gpd_step", rc)
+            self._step_failed("gpd_step", rc)
         return self.obs, self.reward, self.terminated, self.truncated
 
     def step_seq(self, action_slots, n_steps, terminal_obs=True):
@@ -513,8 +558,10 @@ class BatchedAviarySim:
         P = a.numel() // (self.n_drones * self.act_width)
         tptr = self._tobs_ptr if terminal_obs else None
         with torch.cuda.device(self.device):
-            self._call("gpd_step_seq", ctypes.c_void_p(a.data_ptr()), int(P), int(n_steps), *self._out_ptrs, tptr,
-                       _stream(self.device))
+            rc = self._lib.gpd_step_seq(self._h, ctypes.c_void_p(a.data_ptr()), int(P), int(n_steps), *self._out_ptrs,
+                                        tptr, _stream(self.device))
+        if rc != 0:
+            self._step_failed("gpd_step_seq", rc)
         return self.obs, self.reward, self.terminated, self.truncated
 
     def capture_graph(self, actions_seq, terminal_obs=True):
@@ -705,6 +752,43 @@ class BatchedAviarySim:
         with torch.cuda.device(self.device):
             _lib.check("gpd_set_pid_params", self._lib.gpd_set_pid_params(self._h, ctypes.byref(q)))
         self._pid = q
+
+    def set_pid_gains(self, **coeffs):
+        """Every drone's own DSLPIDControl coefficients (``gpd_set_pid_gains``): starts from the gains
+        in force (:meth:`pid_gains`) and replaces the triples given, each broadcast from (3,), (E, 3),
+        (E, 1, 3) or (E, D, 3) (:func:`pid_gain_rows`; the keywords of :meth:`set_pid_coefficients`).
+        While the table is in force, ``cmd_step`` / ``cmd_rollout`` in the ``"vel"`` and ``"waypoint"``
+        modes run each drone's controller on its own row, and :meth:`step` is refused (the RL step
+        reads the sim-wide coefficients).  Installing the first table or clearing it changes which
+        kernel the command step launches: recapture a graph recorded on the other side; a later
+        call that only changes values keeps a captured graph valid.  Synchronous."""
+        rows = pid_gain_rows(self.n_envs, self.drones_per_env, self._pid_gain_rows(), **coeffs)
+        with torch.cuda.device(self.device):
+            self._call("gpd_set_pid_gains", _dptr(rows))
+
+    def _pid_gain_rows(self):
+        rows = np.empty((self.n_drones, _lib.PID_GAIN_COMPS), dtype=np.float64)
+        self._call("gpd_get_pid_gains", _dptr(rows))
+        return rows
+
+    def pid_gains(self):
+        """The coefficients in force for every drone (``gpd_get_pid_gains``): a dict of (E, D, 3)
+        float64 arrays under the keywords of :meth:`set_pid_gains`; the table's values as stored, or
+        the sim-wide triples repeated when no table is in force."""
+        rows = self._pid_gain_rows().reshape(self.n_envs, self.drones_per_env, 6, 3)
+        return {name: np.ascontiguousarray(rows[:, :, k, :]) for k, name in enumerate(PID_GAIN_KEYWORDS)}
+
+    def clear_pid_gains(self):
+        """Put the sim-wide coefficients (:meth:`set_pid_coefficients`) back in force for every drone."""
+        self._call("gpd_set_pid_gains", None)
+
+    def _step_failed(self, name, rc):
+        """The library's refusal of an RL step while a gain table is in force (it launches nothing;
+        whether a table is in force is the library's to know) as NotImplementedError; else GpdError."""
+        msg = self._lib.gpd_last_error().decode(errors="replace")
+        if rc == _lib.GPD_EUNSUPPORTED and "gain table" in msg:
+            raise NotImplementedError(f"{msg}: call clear_pid_gains() first")
+        _lib.check(name, rc)
 
     def step_counters(self):
         out = torch.empty((self.n_envs,), dtype=torch.int32, device=self.device)

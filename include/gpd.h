@@ -25,6 +25,7 @@
  *                        explicit per-substep RPMs (parity / raw-integrator mode).
  *   gpd_get_state20   <- BaseAviary._getDroneStateVector()  envs/BaseAviary.py:541-561
  *   gpd_set_pid_params <- BaseControl.setPIDCoefficients()   control/BaseControl.py:138-177
+ *   gpd_set/get_pid_gains <- the same call on ONE drone's controller object: per-drone coefficients
  *   gpd_get/set_ctrl_state <- the per-drone DSLPIDControl attributes integral_pos_e,
  *                        integral_rpy_e, last_rpy (control/DSLPIDControl.py:65-78)
  *   gpd_pack_layout_of / gpd_handoff_pack / gpd_handoff_unpack <- the hand-off of the
@@ -359,6 +360,32 @@ int gpd_nonfinite(gpd_sim* sim, uint8_t* env_flags, void* stream);
 /* PID action types: replace the controller coefficients of every drone (setPIDCoefficients).
  * Synchronous (uploads the constant block). */
 int gpd_set_pid_params(gpd_sim* sim, const gpd_pid_params* params);
+/* PID action types: every drone's own six coefficient triples, as each drone of the reference owns
+ * a DSLPIDControl object whose setPIDCoefficients (control/BaseControl.py:138-177) sets that one
+ * controller.  gains: host memory [N][18], a row = P_COEFF_FOR(3) I_COEFF_FOR(3) D_COEFF_FOR(3)
+ * P_COEFF_TOR(3) I_COEFF_TOR(3) D_COEFF_TOR(3) (gpd_pid_params' order).  The rows are rounded once to
+ * the sim's real type and uploaded synchronously (as gpd_set_pid_params, gpd_set_env_params).
+ * While a table is in force, gpd_cmd_step and gpd_cmd_rollout run the controller of the
+ * GPD_CMD_VEL and GPD_CMD_WAYPOINT modes on each drone's own row, on envs of any size and across the
+ * launches of a chunked rollout; GPD_CMD_RPM runs no controller and is unaffected.  pwm2rpm_*,
+ * min/max_pwm, mixer, gravity, kf, the control timestep and the speed limit always come from the
+ * sim-wide block; gpd_set_pid_params does not touch the table, and the six triples it sets are
+ * shadowed while a table is in force.
+ *   gains == NULL puts the sim-wide coefficients back in force (the device buffer is kept).
+ *   The device table is allocated at the first install and freed by gpd_destroy only: its address
+ *   never changes, so a graph captured with a table in force sees later installs' values.
+ *   Installing the first table, clearing it, or installing one after a clear changes WHICH kernel
+ *   gpd_cmd_step / gpd_cmd_rollout launch: a graph captured on the other side of that change must
+ *   be recaptured.
+ *   gpd_step and gpd_step_seq read the sim-wide coefficients: with a table in force they return
+ *   GPD_EUNSUPPORTED and launch nothing; after a clear they work as before.
+ *   The table is not part of the checkpoint blob (as the het tables).
+ * GPD_EINVAL: NULL sim; an action type without a controller (so every het sim); a non-finite value
+ * (the message names row and column; the table in force stays what it was). */
+int gpd_set_pid_gains(gpd_sim* sim, const double* gains);
+/* The coefficients in force for every drone, out [N][18] doubles (host memory), rows as above: the
+ * table's values as stored (widened), or the sim-wide six triples repeated when no table is in force. */
+int gpd_get_pid_gains(gpd_sim* sim, double* out);
 /* PID action types: per-drone controller state [N][9] real = integral_pos_e(3)
  * integral_rpy_e(3) last_rpy(3).  Zero at create; NOT cleared by gpd_reset (the reference
  * never resets its controllers after construction). */
