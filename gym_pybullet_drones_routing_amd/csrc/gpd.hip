@@ -4,7 +4,10 @@
 // derives the model constants in double exactly as BaseAviary.py:117-128 does, builds the
 // reset template (INIT_XYZS / INIT_RPYS through the Bullet orientation round trip,
 // BaseAviary.py:194-207, :486-491, :509-519), owns the SoA device state and launches the
-// kernels of gpd_kernels.h on the caller's stream.
+// kernels of gpd_kernels.h on the caller's stream.  The parts of that which need no HIP (the
+// orientation round trip, the derived constants of an env row, the table checks, the built-in
+// parameters, the last-error string) are gpd_host_model.h; here are the sim, the kernel choice,
+// the launches and the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,10 +15,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gpd.h"
+#include "gpd_host_model.h"
 #include "gpd_kernels.h"
 #include "gpd_handoff.h"
 
@@ -29,79 +35,11 @@ static_assert(GPD_CMD_RPM == CMD_RPM && GPD_CMD_VEL == CMD_VEL && GPD_CMD_WAYPOI
 constexpr int kCtrlComps = 9;
 constexpr size_t kLdsBytes = 160 * 1024;   // LDS per workgroup on gfx950
 
-namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
 #define HIP_TRY(expr)                                                                  \
   do {                                                                                 \
     hipError_t e_ = (expr);                                                            \
     if (e_ != hipSuccess) return fail(GPD_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
-
-// ---- host restatements of the Bullet helpers (double), for the reset template only
-void h_quat_to_mat(const double q[4], double m[9]) {
-  const double x = q[0], y = q[1], z = q[2], w = q[3];
-  const double d = x * x + y * y + z * z + w * w, s = 2.0 / d;
-  const double xs = x * s, ys = y * s, zs = z * s;
-  const double wx = w * xs, wy = w * ys, wz = w * zs, xx = x * xs, xy = x * ys, xz = x * zs;
-  const double yy = y * ys, yz = y * zs, zz = z * zs;
-  m[0] = 1.0 - (yy + zz); m[1] = xy - wz; m[2] = xz + wy;
-  m[3] = xy + wz; m[4] = 1.0 - (xx + zz); m[5] = yz - wx;
-  m[6] = xz - wy; m[7] = yz + wx; m[8] = 1.0 - (xx + yy);
-}
-void h_mat_to_quat(const double m[9], double q[4]) {
-  const double tr = m[0] + m[4] + m[8];
-  double t[4];
-  if (tr > 0.0) {
-    double s = std::sqrt(tr + 1.0);
-    t[3] = s * 0.5; s = 0.5 / s;
-    t[0] = (m[7] - m[5]) * s; t[1] = (m[2] - m[6]) * s; t[2] = (m[3] - m[1]) * s;
-  } else {
-    const int i = m[0] < m[4] ? (m[4] < m[8] ? 2 : 1) : (m[0] < m[8] ? 2 : 0);
-    const int j = (i + 1) % 3, k = (i + 2) % 3;
-    double s = std::sqrt(m[i * 4] - m[j * 4] - m[k * 4] + 1.0);
-    t[i] = s * 0.5; s = 0.5 / s;
-    t[3] = (m[k * 3 + j] - m[j * 3 + k]) * s;
-    t[j] = (m[j * 3 + i] + m[i * 3 + j]) * s;
-    t[k] = (m[k * 3 + i] + m[i * 3 + k]) * s;
-  }
-  for (int a = 0; a < 4; ++a) q[a] = t[a];
-}
-void h_roundtrip(const double q[4], double out[4]) {
-  double m[9];
-  h_quat_to_mat(q, m);
-  h_mat_to_quat(m, out);
-}
-void h_euler(const double q[4], double rpy[3]) {
-  const double x = q[0], y = q[1], z = q[2], w = q[3];
-  const double sarg = -2.0 * (x * z - w * y);
-  if (sarg <= -0.99999) {
-    rpy[0] = 0.0; rpy[1] = -0.5 * M_PI; rpy[2] = 2.0 * std::atan2(x, -y);
-  } else if (sarg >= 0.99999) {
-    rpy[0] = 0.0; rpy[1] = 0.5 * M_PI; rpy[2] = 2.0 * std::atan2(-x, y);
-  } else {
-    rpy[1] = std::asin(std::fmin(1.0, std::fmax(-1.0, sarg)));
-    rpy[0] = std::atan2(2.0 * (y * z + w * x), w * w - x * x - y * y + z * z);
-    rpy[2] = std::atan2(2.0 * (x * y + w * z), w * w + x * x - y * y - z * z);
-  }
-}
-void h_quat_from_euler(const double rpy[3], double q[4]) {  // btQuaternion::setEulerZYX
-  const double hy = rpy[2] * 0.5, hp = rpy[1] * 0.5, hr = rpy[0] * 0.5;
-  const double cy = std::cos(hy), sy = std::sin(hy), cp = std::cos(hp), sp = std::sin(hp);
-  const double cr = std::cos(hr), sr = std::sin(hr);
-  q[0] = sr * cp * cy - cr * sp * sy;
-  q[1] = cr * sp * cy + sr * cp * sy;
-  q[2] = cr * cp * sy - sr * sp * cy;
-  q[3] = cr * cp * cy + sr * sp * sy;
-}
-
-}  // namespace
 
 struct gpd_sim {
   gpd_drone_params P;
@@ -159,6 +97,40 @@ struct gpd_sim {
 };
 
 namespace {
+
+// ---- the run-time choices that become template arguments, each made in one place.  f is a
+// generic lambda; it is instantiated for every value listed here, so a caller whose kernels
+// exist for fewer (the RPM action types only, say) asks the narrower helper.
+// the sim's real type: f(R{})
+template <typename F>
+auto by_real(const gpd_sim* s, F&& f) {
+  return s->prec == GPD_F64 ? f(double{}) : f(float{});
+}
+template <int V>
+using int_c = std::integral_constant<int, V>;
+// act code -> ACT_*: f(int_c<ACT>{})
+template <typename F>
+auto with_act(int act, F&& f) {
+  switch (act) {
+    case GPD_ACT_RPM: return f(int_c<ACT_RPM>{});
+    case GPD_ACT_ONE_D_RPM: return f(int_c<ACT_ONE_D_RPM>{});
+    case GPD_ACT_PID: return f(int_c<ACT_PID>{});
+    case GPD_ACT_VEL: return f(int_c<ACT_VEL>{});
+    default: return f(int_c<ACT_ONE_D_PID>{});
+  }
+}
+// the same for the kernels that serve the RPM action types only (het, duo)
+template <typename F>
+auto with_rpm_act(int act, F&& f) {
+  return act == GPD_ACT_RPM ? f(int_c<ACT_RPM>{}) : f(int_c<ACT_ONE_D_RPM>{});
+}
+// D -> MAXT, the block size bound of the multi-wave (wide) kernels: f(int_c<MAXT>{})
+template <typename F>
+auto with_maxt(int D, F&& f) {
+  if (D <= 256) return f(int_c<256>{});
+  if (D <= 512) return f(int_c<512>{});
+  return f(int_c<1024>{});
+}
 
 template <typename R>
 Consts<R> make_consts(const gpd_sim* s) {
@@ -328,46 +300,41 @@ const void* step_het_fn_act(bool multi, int flags) {
     default: return (const void*)step_kernel_het<R, ACT, false, kPfRuntime, POOL...>;
   }
 }
+// the one-wave step_kernel of an action type: the RPM types' flag-set list or the PID types' own
+template <typename R>
+const void* step_fn(int act, bool multi, int flags, bool stream) {
+  return with_act(act, [&](auto a) {
+    constexpr int ACT = decltype(a)::value;
+    if constexpr (act_is_pid(ACT)) return step_fn_pid<R, ACT>(multi, flags);
+    else return step_fn_act<R, ACT>(multi, flags, stream);
+  });
+}
 template <typename R>
 const void* step_kernel_fn(const gpd_sim* s) {
-  if (s->het && s->pool_on)
-    return s->cfg.act_type == GPD_ACT_RPM
-               ? step_het_fn_act<R, ACT_RPM, PoolArgs<R>>(s->D > 1, s->cfg.physics_flags)
-               : step_het_fn_act<R, ACT_ONE_D_RPM, PoolArgs<R>>(s->D > 1, s->cfg.physics_flags);
-  if (s->het)
-    return s->cfg.act_type == GPD_ACT_RPM ? step_het_fn_act<R, ACT_RPM>(s->D > 1, s->cfg.physics_flags)
-                                          : step_het_fn_act<R, ACT_ONE_D_RPM>(s->D > 1, s->cfg.physics_flags);
-  if (s->step_waves == 3)
-    return s->cfg.act_type == GPD_ACT_RPM ? (const void*)step_kernel_duo<R, ACT_RPM, true>
-                                          : (const void*)step_kernel_duo<R, ACT_ONE_D_RPM, true>;
-  if (s->duo)
-    return s->cfg.act_type == GPD_ACT_RPM ? (const void*)step_kernel_duo<R, ACT_RPM, false>
-                                          : (const void*)step_kernel_duo<R, ACT_ONE_D_RPM, false>;
+  const int act = s->cfg.act_type;
   const bool multi = s->D > 1;
+  if (s->het)
+    return with_rpm_act(act, [&](auto a) {
+      constexpr int ACT = decltype(a)::value;
+      return s->pool_on ? step_het_fn_act<R, ACT, PoolArgs<R>>(multi, s->cfg.physics_flags)
+                        : step_het_fn_act<R, ACT>(multi, s->cfg.physics_flags);
+    });
+  if (s->duo)   // two waves, or three with the io wave
+    return with_rpm_act(act, [&](auto a) {
+      constexpr int ACT = decltype(a)::value;
+      return s->step_waves == 3 ? (const void*)step_kernel_duo<R, ACT, true> : (const void*)step_kernel_duo<R, ACT, false>;
+    });
   // the flags the kernel sees (Consts::flags, make_consts)
   const int pf = s->generic_pf ? kPfRuntime
                               : s->cfg.physics_flags | ((s->cfg.physics_flags & GPD_F_BULLET) ? GPD_F_GEOM_WRENCH : 0);
-  switch (s->cfg.act_type) {
-    case GPD_ACT_RPM: return step_fn_act<R, ACT_RPM>(multi, pf, s->stream);
-    case GPD_ACT_ONE_D_RPM: return step_fn_act<R, ACT_ONE_D_RPM>(multi, pf, s->stream);
-    case GPD_ACT_PID: return step_fn_pid<R, ACT_PID>(multi, pf);
-    case GPD_ACT_VEL: return step_fn_pid<R, ACT_VEL>(multi, pf);
-    default: return step_fn_pid<R, ACT_ONE_D_PID>(multi, pf);
-  }
+  return step_fn<R>(act, multi, pf, s->stream);
 }
 
 // static LDS of the run-time-flag step kernel of an action type (the one-wave kernel every sim
 // that is not wide can fall back to: upload_tables)
 template <typename R>
 size_t runtime_step_lds(int act, bool multi) {
-  const void* f;
-  switch (act) {
-    case GPD_ACT_RPM: f = step_fn_act<R, ACT_RPM>(multi, kPfRuntime, false); break;
-    case GPD_ACT_ONE_D_RPM: f = step_fn_act<R, ACT_ONE_D_RPM>(multi, kPfRuntime, false); break;
-    case GPD_ACT_PID: f = step_fn_pid<R, ACT_PID>(multi, kPfRuntime); break;
-    case GPD_ACT_VEL: f = step_fn_pid<R, ACT_VEL>(multi, kPfRuntime); break;
-    default: f = step_fn_pid<R, ACT_ONE_D_PID>(multi, kPfRuntime); break;
-  }
+  const void* f = step_fn<R>(act, multi, kPfRuntime, false);
   hipFuncAttributes fa;
   if (hipFuncGetAttributes(&fa, f) != hipSuccess) {
     (void)hipGetLastError();
@@ -421,19 +388,33 @@ inline unsigned grid_for(long long n, int tpb) { return (unsigned)((n + tpb - 1)
 inline size_t real_size(const gpd_sim* s) { return s->prec == GPD_F64 ? sizeof(double) : sizeof(float); }
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
-template <typename R, int MAXT, bool DC = false>
-const void* step_wide_fn(int act) {
-  switch (act) {
-    case GPD_ACT_RPM: return (const void*)step_kernel_wide<R, ACT_RPM, MAXT, DC>;
-    case GPD_ACT_ONE_D_RPM: return (const void*)step_kernel_wide<R, ACT_ONE_D_RPM, MAXT, DC>;
-    case GPD_ACT_PID: return (const void*)step_kernel_wide<R, ACT_PID, MAXT, DC>;
-    case GPD_ACT_VEL: return (const void*)step_kernel_wide<R, ACT_VEL, MAXT, DC>;
-    default: return (const void*)step_kernel_wide<R, ACT_ONE_D_PID, MAXT, DC>;
-  }
+// Device buffer sizes in bytes, one definition each: create's allocation and clearing, save / load.
+inline size_t state_buf_bytes(const gpd_sim* s) { return (size_t)kStateComps * s->npad * real_size(s); }
+inline size_t ctrl_buf_bytes(const gpd_sim* s) { return (size_t)kCtrlComps * s->npad * real_size(s); }
+inline size_t ring_buf_bytes(const gpd_sim* s) { return (size_t)s->ring_len * s->npad * s->A * sizeof(float); }
+inline size_t ctr_buf_bytes(const gpd_sim* s) { return (size_t)s->E * sizeof(int2); }   // (+ one int2: the ring mark)
+inline size_t tmpl_buf_bytes(const gpd_sim* s) { return s->init_tmpl.size() * real_size(s); }
+inline size_t target_buf_bytes(const gpd_sim* s) { return s->target.size() * real_size(s); }
+inline size_t etab_buf_bytes(const gpd_sim* s) { return (size_t)kHetCols * s->epad * real_size(s); }
+inline size_t pool_desc_bytes(const gpd_sim* s) {
+  return by_real(s, [](auto r) { return sizeof(ResetPool<decltype(r)>); });
 }
-template <typename R, int MAXT>
-const void* integrate_wide_fn(bool traj) {
-  return traj ? (const void*)integrate_kernel_wide<R, true, MAXT> : (const void*)integrate_kernel_wide<R, false, MAXT>;
+
+// step_kernel_wide: the contact instantiation (DC) is the one-wave one (D <= 64)
+template <typename R>
+const void* step_wide_fn(int act, int D, bool dc) {
+  return with_act(act, [&](auto a) {
+    constexpr int ACT = decltype(a)::value;
+    if (dc) return (const void*)step_kernel_wide<R, ACT, kWave, true>;
+    return with_maxt(D, [](auto m) { return (const void*)step_kernel_wide<R, ACT, decltype(m)::value>; });
+  });
+}
+template <typename R>
+const void* integrate_wide_fn(int D, bool traj) {
+  return with_maxt(D, [&](auto m) {
+    constexpr int MAXT = decltype(m)::value;
+    return traj ? (const void*)integrate_kernel_wide<R, true, MAXT> : (const void*)integrate_kernel_wide<R, false, MAXT>;
+  });
 }
 
 // last_clipped_action back from the ring (store_drone_step) before anything reads or replaces
@@ -451,7 +432,7 @@ int settle_last(gpd_sim* s, hipStream_t st) {
   return GPD_OK;
 }
 inline int settle_last_any(gpd_sim* s, hipStream_t st) {
-  return s->prec == GPD_F64 ? settle_last<double>(s, st) : settle_last<float>(s, st);
+  return by_real(s, [&](auto r) { return settle_last<decltype(r)>(s, st); });
 }
 
 template <typename R>
@@ -464,10 +445,7 @@ int launch_step(gpd_sim* s, const float* actions, float* obs, float* reward, uin
   const Consts<R>* c = (const Consts<R>*)s->d_consts;
   if (s->wide) {
     // drone <-> drone contact: the one-wave instantiation with the contact solve (D <= 64)
-    const bool dc = s->dcP > 0;
-    const void* f = dc ? step_wide_fn<R, kWave, true>(s->cfg.act_type)
-                    : s->D <= 256 ? step_wide_fn<R, 256>(s->cfg.act_type)
-                    : (s->D <= 512 ? step_wide_fn<R, 512>(s->cfg.act_type) : step_wide_fn<R, 1024>(s->cfg.act_type));
+    const void* f = step_wide_fn<R>(s->cfg.act_type, s->D, s->dcP > 0);
     void* args[] = {(void*)&v, (void*)&io, (void*)&c};
     const int ge = s->tpb / s->D;   // envs per workgroup
     HIP_TRY(hipLaunchKernel(f, dim3((s->E + ge - 1) / ge), dim3((s->tpb + kWave - 1) / kWave * kWave), args, 0, st));
@@ -514,8 +492,7 @@ int launch_integrate(gpd_sim* s, const void* rpm, int n_sub, void* traj, hipStre
   const R* r = (const R*)rpm;
   R* tr = (R*)traj;
   if (s->wide && s->D > kWave) {   // (long-history envs of <= 64 drones: the one-wave kernels, no tile)
-    const void* fw = s->D <= 256 ? integrate_wide_fn<R, 256>(tr != nullptr)
-                     : (s->D <= 512 ? integrate_wide_fn<R, 512>(tr != nullptr) : integrate_wide_fn<R, 1024>(tr != nullptr));
+    const void* fw = integrate_wide_fn<R>(s->D, tr != nullptr);
     void* args[] = {(void*)&v, (void*)&c, (void*)&r, (void*)&n_sub, (void*)&tr};
     HIP_TRY(hipLaunchKernel(fw, dim3(s->E), dim3((s->D + kWave - 1) / kWave * kWave), args, 0, st));
     return GPD_OK;
@@ -552,36 +529,38 @@ int launch_integrate(gpd_sim* s, const void* rpm, int n_sub, void* traj, hipStre
   return GPD_OK;
 }
 
-// gpd_cmd_step.  Instantiations: the RPM mode on plain DYN and on the run-time flags, the
-// controller modes on the run-time flags only (every one that carries the contact code is
-// expensive to compile).
-template <typename R>
-const void* cmd_step_fn(bool multi, bool plain, bool ctrl) {
-  if (ctrl)
-    return multi ? (const void*)cmd_step_kernel<R, true, kPfRuntime, true>
-                 : (const void*)cmd_step_kernel<R, false, kPfRuntime, true>;
-  if (multi)
-    return plain ? (const void*)cmd_step_kernel<R, true, 0, false>
-                 : (const void*)cmd_step_kernel<R, true, kPfRuntime, false>;
-  return plain ? (const void*)cmd_step_kernel<R, false, 0, false>
-               : (const void*)cmd_step_kernel<R, false, kPfRuntime, false>;
+// gpd_cmd_step / gpd_cmd_rollout.  Instantiations: the RPM mode on plain DYN and on the run-time
+// flags, the controller modes on the run-time flags only (every one that carries the contact code
+// is expensive to compile), and the controller modes once more with PG, which read the kernels'
+// last argument while a per-drone gain table is in force (gpd_set_pid_gains).  K names the kernel:
+// CmdStepK or CmdRolloutK, the same choice on either.
+template <typename K, bool MULTI>
+const void* cmd_fn_multi(bool plain, bool ctrl, bool pg) {
+  if (pg) return K::template fn<MULTI, kPfRuntime, true, true>();
+  if (ctrl) return K::template fn<MULTI, kPfRuntime, true, false>();
+  return plain ? K::template fn<MULTI, 0, false, false>() : K::template fn<MULTI, kPfRuntime, false, false>();
 }
-template <typename R, int MAXT>
-const void* cmd_step_wide_fn(bool ctrl) {
-  return ctrl ? (const void*)cmd_step_kernel_wide<R, MAXT, true> : (const void*)cmd_step_kernel_wide<R, MAXT, false>;
-}
-// The controller modes while a per-drone gain table is in force (gpd_set_pid_gains): the same
-// controller instantiations with PG, which read the kernels' last argument.
-template <typename R>
-const void* cmd_step_pg_fn(bool multi) {
-  return multi ? (const void*)cmd_step_kernel<R, true, kPfRuntime, true, true>
-               : (const void*)cmd_step_kernel<R, false, kPfRuntime, true, true>;
+template <typename K>
+const void* cmd_fn(bool multi, bool plain, bool ctrl, bool pg) {
+  return multi ? cmd_fn_multi<K, true>(plain, ctrl, pg) : cmd_fn_multi<K, false>(plain, ctrl, pg);
 }
 template <typename R>
-const void* cmd_step_wide_pg_fn(int D) {
-  return D <= 256 ? (const void*)cmd_step_kernel_wide<R, 256, true, true>
-                  : (D <= 512 ? (const void*)cmd_step_kernel_wide<R, 512, true, true>
-                              : (const void*)cmd_step_kernel_wide<R, 1024, true, true>);
+struct CmdStepK {
+  template <bool MULTI, int PF, bool CTRL, bool PG>
+  static const void* fn() { return (const void*)cmd_step_kernel<R, MULTI, PF, CTRL, PG>; }
+};
+template <typename R>
+struct CmdRolloutK {
+  template <bool MULTI, int PF, bool CTRL, bool PG>
+  static const void* fn() { return (const void*)cmd_rollout_kernel<R, MULTI, PF, CTRL, PG>; }
+};
+template <typename R>
+const void* cmd_step_wide_fn(int D, bool ctrl, bool pg) {
+  return with_maxt(D, [&](auto m) {
+    constexpr int MAXT = decltype(m)::value;
+    if (pg) return (const void*)cmd_step_kernel_wide<R, MAXT, true, true>;
+    return ctrl ? (const void*)cmd_step_kernel_wide<R, MAXT, true> : (const void*)cmd_step_kernel_wide<R, MAXT, false>;
+  });
 }
 
 template <typename R>
@@ -597,28 +576,13 @@ int launch_cmd_step(gpd_sim* s, int mode, const void* actions, void* obs20, hipS
   const R* g = pg ? (const R*)s->d_gains : nullptr;   // read by the PG instantiations only
   void* args[] = {(void*)&v, (void*)&c, (void*)&actions, (void*)&mode, (void*)&max_rpm, (void*)&o, (void*)&g};
   if (s->D > kWave) {
-    const void* fw = pg ? cmd_step_wide_pg_fn<R>(s->D)
-                     : s->D <= 256 ? cmd_step_wide_fn<R, 256>(ctrl)
-                     : (s->D <= 512 ? cmd_step_wide_fn<R, 512>(ctrl) : cmd_step_wide_fn<R, 1024>(ctrl));
+    const void* fw = cmd_step_wide_fn<R>(s->D, ctrl, pg);
     HIP_TRY(hipLaunchKernel(fw, dim3(s->E), dim3((s->D + kWave - 1) / kWave * kWave), args, 0, st));
     return GPD_OK;
   }
-  const void* f = pg ? cmd_step_pg_fn<R>(s->D > 1) : cmd_step_fn<R>(s->D > 1, s->cfg.physics_flags == 0, ctrl);
+  const void* f = cmd_fn<CmdStepK<R>>(s->D > 1, s->cfg.physics_flags == 0, ctrl, pg);
   HIP_TRY(hipLaunchKernel(f, dim3(grid_for(s->N, s->tpb)), dim3(kWave), args, 0, st));
   return GPD_OK;
-}
-
-// gpd_cmd_rollout: cmd_step_fn's instantiations of the multi-step kernel.
-template <typename R>
-const void* cmd_rollout_fn(bool multi, bool plain, bool ctrl) {
-  if (ctrl)
-    return multi ? (const void*)cmd_rollout_kernel<R, true, kPfRuntime, true>
-                 : (const void*)cmd_rollout_kernel<R, false, kPfRuntime, true>;
-  if (multi)
-    return plain ? (const void*)cmd_rollout_kernel<R, true, 0, false>
-                 : (const void*)cmd_rollout_kernel<R, true, kPfRuntime, false>;
-  return plain ? (const void*)cmd_rollout_kernel<R, false, 0, false>
-               : (const void*)cmd_rollout_kernel<R, false, kPfRuntime, false>;
 }
 
 template <typename R>
@@ -654,9 +618,7 @@ int launch_cmd_rollout(gpd_sim* s, int mode, const void* actions, int n_steps, i
   const SimView<R> v = make_view<R>(s);
   const Consts<R>* c = (const Consts<R>*)s->d_consts;
   const bool pg = mode != GPD_CMD_RPM && s->gains_on;
-  const void* f = pg ? (s->D > 1 ? (const void*)cmd_rollout_kernel<R, true, kPfRuntime, true, true>
-                                 : (const void*)cmd_rollout_kernel<R, false, kPfRuntime, true, true>)
-                     : cmd_rollout_fn<R>(s->D > 1, s->cfg.physics_flags == 0, mode != GPD_CMD_RPM);
+  const void* f = cmd_fn<CmdRolloutK<R>>(s->D > 1, s->cfg.physics_flags == 0, mode != GPD_CMD_RPM, pg);
   const R* g = pg ? (const R*)s->d_gains : nullptr;   // read by the PG instantiations only
   R max_rpm = (R)s->K.max_rpm;
   for (int t0 = 0; t0 < n_steps; t0 += chunk) {
@@ -722,22 +684,10 @@ int launch_set_raw(gpd_sim* s, const void* in, hipStream_t st) {
 
 void free_sim(gpd_sim* s) {
   if (!s) return;
-  if (s->d_state) (void)hipFree(s->d_state);
-  if (s->d_ctrl) (void)hipFree(s->d_ctrl);
-  if (s->d_ring) (void)hipFree(s->d_ring);
-  if (s->d_ctr) (void)hipFree(s->d_ctr);
-  if (s->d_init) (void)hipFree(s->d_init);
-  if (s->d_target) (void)hipFree(s->d_target);
-  if (s->d_consts) (void)hipFree(s->d_consts);
-  if (s->d_etab) (void)hipFree(s->d_etab);
-  if (s->d_draws) (void)hipFree(s->d_draws);
-  if (s->d_pool) (void)hipFree(s->d_pool);
-  if (s->d_pool_rows) (void)hipFree(s->d_pool_rows);
-  if (s->d_pool_init) (void)hipFree(s->d_pool_init);
-  if (s->d_pool_target) (void)hipFree(s->d_pool_target);
-  if (s->d_dc_tab) (void)hipFree(s->d_dc_tab);
-  if (s->d_dc_rows) (void)hipFree(s->d_dc_rows);
-  if (s->d_gains) (void)hipFree(s->d_gains);
+  for (void* p : {s->d_state, s->d_ctrl, (void*)s->d_ring, (void*)s->d_ctr, s->d_init, s->d_target, s->d_consts, s->d_etab,
+                  (void*)s->d_draws, s->d_pool, s->d_pool_rows, s->d_pool_init, s->d_pool_target, (void*)s->d_dc_tab,
+                  s->d_dc_rows, s->d_gains})
+    if (p) (void)hipFree(p);
   delete s;
 }
 
@@ -752,87 +702,6 @@ struct HetArgs {
   const double* rpys;           // [E][D][3] or null
 };
 
-// the reset template of one drone: INIT_XYZS and the orientation the client stores
-// (BaseAviary.py:194-207, :486-491, :509-519)
-void pose_template(const double xyz[3], const double rpy[3], double t[10]) {
-  double q0[4], qraw[4], qn[4], e[3];
-  h_quat_from_euler(rpy, q0);
-  h_roundtrip(q0, qraw);  // loadURDF stores the orientation through a btTransform
-  h_roundtrip(qraw, qn);  // readback (:517)
-  h_euler(qn, e);         // :518
-  t[0] = xyz[0]; t[1] = xyz[1]; t[2] = xyz[2];
-  t[3] = qraw[0]; t[4] = qraw[1]; t[5] = qraw[2]; t[6] = qraw[3];
-  t[7] = e[0]; t[8] = e[1]; t[9] = e[2];
-}
-
-gpd_env_params env_row_of(const gpd_drone_params& P) {
-  return gpd_env_params{P.m, P.arm, P.thrust2weight, P.ixx, P.iyy, P.izz, P.kf, P.km,
-                        P.gnd_eff_coeff, P.drag_coeff_xy, P.drag_coeff_z};
-}
-
-// self.MAX_RPM**2 as Python evaluates it: libm's pow(x, 2.0), which is not correctly rounded in
-// every libm and then differs from x*x in the last bit (seen on one row in a thousand); the
-// exponent is opaque so that the compiler cannot turn the call into a multiply
-double py_square(double x) {
-  volatile double two = 2.0;
-  return std::pow(x, two);
-}
-
-// BaseAviary.py:117-128 for one env row, operation for operation (no FP contraction)
-void derive_row(const gpd_drone_params& base, const gpd_env_params& r, gpd_constants& K) {
-#pragma clang fp contract(off)
-  std::memset(&K, 0, sizeof(K));
-  K.gravity = 9.8 * r.m;
-  K.hover_rpm = std::sqrt(K.gravity / (4 * r.kf));
-  K.max_rpm = std::sqrt((r.thrust2weight * K.gravity) / (4 * r.kf));
-  const double mr2 = py_square(K.max_rpm);
-  K.max_thrust = 4 * r.kf * mr2;
-  K.max_xy_torque = base.model == GPD_MODEL_CF2P ? r.arm * r.kf * mr2 : (2 * r.arm * r.kf * mr2) / std::sqrt(2.0);
-  K.max_z_torque = 2 * r.km * mr2;
-  K.gnd_eff_h_clip = 0.25 * base.prop_radius * std::sqrt((15 * mr2 * r.kf * r.gnd_eff_coeff) / K.max_thrust);
-}
-
-int check_env_rows(const char* fn, const gpd_env_params* rows, int n, const char* unit = "env") {
-  static const char* const names[11] = {"m", "arm", "thrust2weight", "ixx", "iyy", "izz", "kf", "km",
-                                        "gnd_eff_coeff", "drag_coeff_xy", "drag_coeff_z"};
-  for (int e = 0; e < n; ++e) {
-    const double* f = &rows[e].m;
-    for (int k = 0; k < 11; ++k) {
-      const bool aero = k >= 8;   // the three aero coefficients may be 0
-      if (!std::isfinite(f[k]) || f[k] < 0.0 || (!aero && f[k] == 0.0))
-        return fail(GPD_EINVAL, std::string(fn) + ": env_params field " + names[k] + " of " + unit + " " + std::to_string(e) +
-                                    " must be finite and " + (aero ? ">= 0" : "> 0"));
-    }
-  }
-  return GPD_OK;
-}
-static_assert(sizeof(gpd_env_params) == 11 * sizeof(double), "gpd_env_params is 11 packed doubles");
-
-int check_poses(const char* fn, const char* what, const double* p, long long n_drones, int D, const char* unit = "env") {
-  if (!p) return GPD_OK;
-  for (long long i = 0; i < n_drones * 3; ++i)
-    if (!std::isfinite(p[i]))
-      return fail(GPD_EINVAL, std::string(fn) + ": " + what + " of " + unit + " " + std::to_string(i / (3LL * D)) +
-                                  " drone " + std::to_string((i / 3) % D) + " is not finite");
-  return GPD_OK;
-}
-
-// [n][D][10] templates and [n][D][3] targets from n x D poses (a het sim's envs, or a reset pool)
-void pose_tables(int task, size_t n_sets, int D, const double* xyzs, const double* rpys, double* tmpl, double* target) {
-  for (size_t e = 0; e < n_sets; ++e)
-    for (int d = 0; d < D; ++d) {
-      const size_t n = e * D + d;
-      const double* xyz = &xyzs[n * 3];
-      pose_template(xyz, &rpys[n * 3], &tmpl[n * 10]);
-      double* tg = &target[n * 3];
-      tg[0] = tg[1] = tg[2] = 0.0;
-      if (task == GPD_TASK_HOVER) {           // HoverAviary.py:51
-        tg[2] = 1.0;
-      } else if (task == GPD_TASK_MULTIHOVER) {  // MultiHoverAviary.py:71
-        tg[0] = xyz[0]; tg[1] = xyz[1]; tg[2] = xyz[2] + 1.0 / (d + 1);
-      }
-    }
-}
 // [E][D][10] templates and [E][D][3] targets from the stored het poses
 void het_templates(gpd_sim* s) {
   pose_tables(s->cfg.task, (size_t)s->E, s->D, s->het_xyz.data(), s->het_rpy.data(), s->init_tmpl.data(),
@@ -934,224 +803,71 @@ int env_table_to_host(gpd_sim* s, double* out) {
   return GPD_OK;
 }
 
-int create_impl(const gpd_drone_params* params, const gpd_config* cfg, const HetArgs* het, gpd_sim** out);
+// ---- the create path (gpd_create, gpd_create_het), in stages.  fn is the entry point's name, for
+// the messages; the sim is held by a SimPtr from its allocation on, so every early return frees it.
+struct SimDeleter { void operator()(gpd_sim* s) const { free_sim(s); } };
+using SimPtr = std::unique_ptr<gpd_sim, SimDeleter>;
 
-}  // namespace
-
-extern "C" {
-
-int gpd_abi_version(void) { return GPD_ABI_VERSION; }
-
-const char* gpd_last_error(void) { return g_err.c_str(); }
-
-int gpd_default_params(int model, gpd_drone_params* out) {
-  if (!out) return fail(GPD_EINVAL, "gpd_default_params: out is NULL");
-  gpd_drone_params p;
-  std::memset(&p, 0, sizeof(p));
-  p.model = model;
-  // <properties> common to the three URDFs (cf2x.urdf:5)
-  p.gnd_eff_coeff = 11.36859; p.drag_coeff_xy = 9.1785e-7; p.drag_coeff_z = 10.311e-7;
-  p.dw_coeff_1 = 2267.18; p.dw_coeff_2 = .16; p.dw_coeff_3 = -.11;
-  p.collision_h = .025; p.collision_r = .06; p.collision_z_offset = 0.0;  // collision cylinder
-  double pp[4][3];
-  if (model == GPD_MODEL_CF2X || model == GPD_MODEL_CF2P) {             // cf2x.urdf / cf2p.urdf
-    p.arm = 0.0397; p.kf = 3.16e-10; p.km = 7.94e-12; p.thrust2weight = 2.25; p.max_speed_kmh = 30;
-    p.prop_radius = 2.31348e-2; p.m = 0.027;
-    if (model == GPD_MODEL_CF2X) {
-      p.ixx = 1.4e-5; p.iyy = 1.4e-5; p.izz = 2.17e-5;
-      const double c[4][3] = {{0.028, -0.028, 0}, {-0.028, -0.028, 0}, {-0.028, 0.028, 0}, {0.028, 0.028, 0}};
-      std::memcpy(pp, c, sizeof(pp));
-    } else {
-      p.ixx = 2.3951e-5; p.iyy = 2.3951e-5; p.izz = 3.2347e-5;
-      const double c[4][3] = {{0.0397, 0, 0}, {0, 0.0397, 0}, {-0.0397, 0, 0}, {0, -0.0397, 0}};
-      std::memcpy(pp, c, sizeof(pp));
-    }
-  } else if (model == GPD_MODEL_RACE) {                                   // racer.urdf
-    p.arm = 0.109; p.kf = 8.47e-9; p.km = 2.13e-11; p.thrust2weight = 4.17; p.max_speed_kmh = 200;
-    p.prop_radius = 12.7e-2; p.m = 0.830; p.ixx = .003113; p.iyy = .003113; p.izz = .003113;
-    const double c[4][3] = {{0.0850, 0.0675, 0}, {-0.0850, 0.0675, 0}, {-0.085, -0.0675, 0}, {0.085, -0.0675, 0}};
-    std::memcpy(pp, c, sizeof(pp));
-  } else {
-    return fail(GPD_EINVAL, "gpd_default_params: unknown drone model");
-  }
-  std::memcpy(p.prop_pos, pp, sizeof(pp));
-  *out = p;
-  return GPD_OK;
-}
-
-int gpd_create(const gpd_drone_params* params, const gpd_config* cfg, gpd_sim** out) {
-  return create_impl(params, cfg, nullptr, out);
-}
-
-int gpd_create_het(const gpd_drone_params* params, const gpd_config* cfg, const gpd_env_params* env_params_host,
-                   const double* init_xyzs_host, const double* init_rpys_host, gpd_sim** out) {
-  if (!params || !cfg || !out) return fail(GPD_EINVAL, "gpd_create_het: NULL argument");
-  *out = nullptr;
-  const gpd_config& C = *cfg;
-  // what a het sim supports, then every row and pose: all before the first device call
-  if (C.n_envs < 1) return fail(GPD_EINVAL, "gpd_create_het: n_envs must be >= 1");
-  if (C.drones_per_env < 1) return fail(GPD_EINVAL, "gpd_create_het: drones_per_env must be >= 1");
-  if (C.physics_flags & GPD_F_BULLET)
-    return fail(GPD_EUNSUPPORTED, "gpd_create_het: GPD_F_BULLET (Physics.PYB*) is not supported with per-env "
-                                  "parameters: the contact solves hold mass and inertia in derived rows; use the DYN "
-                                  "integrator (Physics.DYN)");
-  if (C.physics_flags & ~kHetFlags) return fail(GPD_EINVAL, "gpd_create_het: unknown or contact-only physics flag");
-  if (C.act_type != GPD_ACT_RPM && C.act_type != GPD_ACT_ONE_D_RPM)
-    return fail(GPD_EUNSUPPORTED, "gpd_create_het: the PID action types are not supported with per-env parameters "
-                                  "(DSLPIDControl is tuned for the nominal drone); use GPD_ACT_RPM or GPD_ACT_ONE_D_RPM");
-  if (C.drones_per_env > kWave)
-    return fail(GPD_EUNSUPPORTED, "gpd_create_het: drones_per_env > 64 needs the multi-wave step kernel, which has no "
-                                  "per-env parameters");
-  if (C.ctrl_freq >= 2 &&
-      (size_t)step_tile_bytes(act_width(C.act_type), C.ctrl_freq / 2) + kHetStaticLds > kLdsBytes)
-    return fail(GPD_EUNSUPPORTED, "gpd_create_het: the action history (ctrl_freq // 2 slots) does not fit the one-wave "
-                                  "step kernel's observation tile; the multi-wave kernel has no per-env parameters");
-  const long long N = (long long)C.n_envs * C.drones_per_env;
-  int rc = env_params_host ? check_env_rows("gpd_create_het", env_params_host, C.n_envs) : GPD_OK;
-  if (rc == GPD_OK) rc = check_poses("gpd_create_het", "init_xyzs", init_xyzs_host, N, C.drones_per_env);
-  if (rc == GPD_OK) rc = check_poses("gpd_create_het", "init_rpys", init_rpys_host, N, C.drones_per_env);
-  if (rc != GPD_OK) return rc;
-  const HetArgs het{env_params_host, init_xyzs_host, init_rpys_host};
-  rc = create_impl(params, cfg, &het, out);
-  // the shared checks' messages under this entry point's name
-  if (rc != GPD_OK && g_err.compare(0, 11, "gpd_create:") == 0) g_err.replace(0, 10, "gpd_create_het");
-  return rc;
-}
-
-int gpd_set_env_params(gpd_sim* sim, const gpd_env_params* rows_host) {
-  if (!sim || !rows_host) return fail(GPD_EINVAL, "gpd_set_env_params: NULL argument");
-  if (!sim->het) return fail(GPD_EINVAL, "gpd_set_env_params: not a het sim (create it with gpd_create_het)");
-  int rc = check_env_rows("gpd_set_env_params", rows_host, sim->E);
-  if (rc != GPD_OK) return rc;
-  // a last action still in the ring (store-policy bit 2) is rebuilt from the env's hover column:
-  // settle it with the rows the steps ran on, before they are replaced
-  rc = settle_last_any(sim, 0);
-  if (rc != GPD_OK) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  rc = fold_draws(sim, 1);   // every row index back to -1: the rows in force are the new ones
-  if (rc != GPD_OK) return rc;
-  sim->env_rows.assign(rows_host, rows_host + sim->E);
-  return sim->prec == GPD_F64 ? upload_env_table<double>(sim) : upload_env_table<float>(sim);
-}
-
-int gpd_set_env_init(gpd_sim* sim, const double* xyzs_host, const double* rpys_host) {
-  if (!sim) return fail(GPD_EINVAL, "gpd_set_env_init: NULL sim");
-  if (!sim->het) return fail(GPD_EINVAL, "gpd_set_env_init: not a het sim (create it with gpd_create_het)");
-  int rc = check_poses("gpd_set_env_init", "init_xyzs", xyzs_host, sim->N, sim->D);
-  if (rc == GPD_OK) rc = check_poses("gpd_set_env_init", "init_rpys", rpys_host, sim->N, sim->D);
-  if (rc != GPD_OK) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  rc = fold_draws(sim, 2);   // a NULL table keeps the poses in force; every pose index back to -1
-  if (rc != GPD_OK) return rc;
-  if (xyzs_host) sim->het_xyz.assign(xyzs_host, xyzs_host + (size_t)sim->N * 3);
-  if (rpys_host) sim->het_rpy.assign(rpys_host, rpys_host + (size_t)sim->N * 3);
-  het_templates(sim);
-  return sim->prec == GPD_F64 ? upload_tables<double>(sim) : upload_tables<float>(sim);
-}
-
-int gpd_env_derive(const gpd_drone_params* base, const gpd_env_params* rows, int n, gpd_constants* out) {
-  if (!base || !rows || !out || n < 0) return fail(GPD_EINVAL, "gpd_env_derive: NULL argument or n < 0");
-  for (int i = 0; i < n; ++i) derive_row(*base, rows[i], out[i]);
-  return GPD_OK;
-}
-
-int gpd_reset_pool_draw(unsigned seed, int stream, long long env, int episode, int n) {
-  if (n < 1) return 0;
-  return pool_draw(seed, (unsigned)stream, (unsigned)env, (unsigned)episode, (unsigned)n);
-}
-
-int gpd_set_reset_pool(gpd_sim* sim, const gpd_env_params* rows_host, int n_rows, const double* xyzs_host,
-                       const double* rpys_host, int n_poses, unsigned seed) {
-  if (!sim) return fail(GPD_EINVAL, "gpd_set_reset_pool: NULL sim");
-  if (!sim->het) return fail(GPD_EINVAL, "gpd_set_reset_pool: not a het sim (create it with gpd_create_het)");
-  if (n_rows < 0 || n_poses < 0) return fail(GPD_EINVAL, "gpd_set_reset_pool: n_rows and n_poses must be >= 0");
-  if (n_rows > 0 && !rows_host) return fail(GPD_EINVAL, "gpd_set_reset_pool: rows_host is NULL but n_rows > 0");
-  if (n_poses > 0 && !xyzs_host) return fail(GPD_EINVAL, "gpd_set_reset_pool: xyzs_host is NULL but n_poses > 0");
-  const long long nq = (long long)n_poses * sim->D;
-  int rc = check_env_rows("gpd_set_reset_pool", rows_host, n_rows, "pool row");
-  if (rc == GPD_OK) rc = check_poses("gpd_set_reset_pool", "xyzs", n_poses ? xyzs_host : nullptr, nq, sim->D, "pool pose");
-  if (rc == GPD_OK) rc = check_poses("gpd_set_reset_pool", "rpys", n_poses ? rpys_host : nullptr, nq, sim->D, "pool pose");
-  if (rc != GPD_OK) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  rc = fold_draws(sim, 3);   // what the old pools gave stays in force, as the env's own
-  if (rc != GPD_OK) return rc;
-  sim->pool_rows.assign(rows_host, rows_host + n_rows);
-  sim->pool_xyz.assign(xyzs_host, xyzs_host + nq * 3);
-  if (n_poses && rpys_host) sim->pool_rpy.assign(rpys_host, rpys_host + nq * 3);
-  else sim->pool_rpy.assign((size_t)nq * 3, 0.0);
-  return sim->prec == GPD_F64 ? upload_pool<double>(sim, seed) : upload_pool<float>(sim, seed);
-}
-
-int gpd_get_reset_draws(gpd_sim* sim, int* out_dev, void* stream) {
-  if (!sim || !out_dev) return fail(GPD_EINVAL, "gpd_get_reset_draws: NULL argument");
-  if (!sim->het) return fail(GPD_EINVAL, "gpd_get_reset_draws: not a het sim (create it with gpd_create_het)");
-  HIP_TRY(hipMemcpyAsync(out_dev, sim->d_draws, (size_t)sim->E * 3 * sizeof(int), hipMemcpyDeviceToDevice,
-                         (hipStream_t)stream));
-  return GPD_OK;
-}
-
-int gpd_get_env_table(gpd_sim* sim, double* out_host) {
-  if (!sim || !out_host) return fail(GPD_EINVAL, "gpd_get_env_table: NULL argument");
-  if (!sim->het) return fail(GPD_EINVAL, "gpd_get_env_table: not a het sim (create it with gpd_create_het)");
-  HIP_TRY(hipDeviceSynchronize());
-  return sim->prec == GPD_F64 ? env_table_to_host<double>(sim, out_host) : env_table_to_host<float>(sim, out_host);
-}
-
-}  // extern "C"
-
-namespace {
-
-int create_impl(const gpd_drone_params* params, const gpd_config* cfg, const HetArgs* het, gpd_sim** out) {
-  if (!params || !cfg || !out) return fail(GPD_EINVAL, "gpd_create: NULL argument");
-  *out = nullptr;
-  const gpd_config& C = *cfg;
-  if (C.n_envs < 1) return fail(GPD_EINVAL, "gpd_create: n_envs must be >= 1");
+// what every sim needs of its configuration: all before the first device call
+int validate_config(const std::string& fn, const gpd_drone_params* params, const gpd_config& C) {
+  if (C.n_envs < 1) return fail(GPD_EINVAL, fn + ": n_envs must be >= 1");
   if (C.drones_per_env < 1 || C.drones_per_env > kWideMax)
-    return fail(GPD_EINVAL, "gpd_create: drones_per_env must be in [1, 1024]");
-  if (C.pyb_freq < 1 || C.ctrl_freq < 1) return fail(GPD_EINVAL, "gpd_create: frequencies must be >= 1");
+    return fail(GPD_EINVAL, fn + ": drones_per_env must be in [1, 1024]");
+  if (C.pyb_freq < 1 || C.ctrl_freq < 1) return fail(GPD_EINVAL, fn + ": frequencies must be >= 1");
   if (C.pyb_freq % C.ctrl_freq != 0)
     return fail(GPD_EINVAL, "[ERROR] in BaseAviary.__init__(), pyb_freq is not divisible by env_freq.");
   if (C.ctrl_freq / 2 < 1)
-    return fail(GPD_EUNSUPPORTED, "gpd_create: ctrl_freq//2 == 0 gives an empty action buffer (unsupported)");
-  if (C.act_type < GPD_ACT_RPM || C.act_type > GPD_ACT_ONE_D_PID) return fail(GPD_EINVAL, "gpd_create: bad act_type");
+    return fail(GPD_EUNSUPPORTED, fn + ": ctrl_freq//2 == 0 gives an empty action buffer (unsupported)");
+  if (C.act_type < GPD_ACT_RPM || C.act_type > GPD_ACT_ONE_D_PID) return fail(GPD_EINVAL, fn + ": bad act_type");
   const bool pid = act_is_pid(C.act_type);
   if (pid && params->model != GPD_MODEL_CF2X && params->model != GPD_MODEL_CF2P)  // BaseRLAviary.py:75-78
     return fail(GPD_EUNSUPPORTED,
                 "[ERROR] in BaseRLAviary.__init()__, no controller is available for the specified drone_model");
-  if (C.task < GPD_TASK_NONE || C.task > GPD_TASK_MULTIHOVER) return fail(GPD_EINVAL, "gpd_create: bad task");
+  if (C.task < GPD_TASK_NONE || C.task > GPD_TASK_MULTIHOVER) return fail(GPD_EINVAL, fn + ": bad task");
   if (C.task == GPD_TASK_HOVER && C.drones_per_env != 1)
-    return fail(GPD_EINVAL, "gpd_create: HoverAviary is single-drone (drones_per_env must be 1)");
-  if (C.precision != GPD_F32 && C.precision != GPD_F64) return fail(GPD_EINVAL, "gpd_create: bad precision");
+    return fail(GPD_EINVAL, fn + ": HoverAviary is single-drone (drones_per_env must be 1)");
+  if (C.precision != GPD_F32 && C.precision != GPD_F64) return fail(GPD_EINVAL, fn + ": bad precision");
   if (C.solver_iterations < 0 || C.solver_iterations > 1000)
-    return fail(GPD_EINVAL, "gpd_create: solver_iterations must be 0 (default) or in [1, 1000]");
-  if (!std::isfinite(C.solver_residual)) return fail(GPD_EINVAL, "gpd_create: solver_residual must be finite");
+    return fail(GPD_EINVAL, fn + ": solver_iterations must be 0 (default) or in [1, 1000]");
+  if (!std::isfinite(C.solver_residual)) return fail(GPD_EINVAL, fn + ": solver_residual must be finite");
   if ((C.physics_flags & GPD_F_BULLET) && C.drones_per_env > kWave && !(C.physics_flags & GPD_F_NO_DRONE_CONTACT))
     return fail(GPD_EUNSUPPORTED,
-                "gpd_create: drone <-> drone contact is implemented for envs of up to 64 drones; pass "
+                fn + ": drone <-> drone contact is implemented for envs of up to 64 drones; pass "
                 "GPD_F_NO_DRONE_CONTACT (aero 'no_drone_contact') for larger PYB* envs");
   if (C.physics_flags & ~(GPD_F_GND | GPD_F_DRAG | GPD_F_DW | GPD_F_GEOM_WRENCH | GPD_F_BULLET | GPD_F_NO_PLANE |
                           GPD_F_NO_DRONE_CONTACT))
-    return fail(GPD_EINVAL, "gpd_create: unknown physics flag");
+    return fail(GPD_EINVAL, fn + ": unknown physics flag");
   if (params->model < GPD_MODEL_CF2X || params->model > GPD_MODEL_RACE)
-    return fail(GPD_EINVAL, "gpd_create: unknown drone model");
-  const long long Nll = (long long)C.n_envs * C.drones_per_env;
-  if (Nll > (1LL << 31) - 64) return fail(GPD_EINVAL, "gpd_create: too many drones");
+    return fail(GPD_EINVAL, fn + ": unknown drone model");
+  if ((long long)C.n_envs * C.drones_per_env > (1LL << 31) - 64) return fail(GPD_EINVAL, fn + ": too many drones");
+  return GPD_OK;
+}
 
-  gpd_sim* s = new gpd_sim();
+// a sim of a validated configuration, its shape filled in and nothing on the device yet
+SimPtr new_sim(const gpd_drone_params* params, const gpd_config& C, bool het) {
+  SimPtr s(new gpd_sim());
   s->P = *params;
   s->cfg = C;
   s->cfg.init_xyzs_host = nullptr;
   s->cfg.init_rpys_host = nullptr;
   s->E = C.n_envs;
   s->D = C.drones_per_env;
-  s->N = (int)Nll;
+  s->N = C.n_envs * C.drones_per_env;
   s->A = act_width(C.act_type);
-  gpd_default_pid_params(&s->pid);
+  default_pid_params(&s->pid);
   s->ring_len = C.ctrl_freq / 2;  // ACTION_BUFFER_SIZE = int(ctrl_freq//2)  BaseRLAviary.py:66
   s->W = 12 + s->ring_len * s->A;
   s->nsub = C.pyb_freq / C.ctrl_freq;
   s->prec = C.precision;
-  s->het = het != nullptr;
+  s->het = het;
+  return s;
+}
+
+// The launch policy: the block shape, the wide / duo / stream kernels, the store policy, nc_magic
+// and the downwash pairs.  The thresholds are measured; the comments carry the figures.
+int plan_launch(const std::string& fn, gpd_sim* s) {
+  const gpd_config& C = s->cfg;
+  const long long Nll = s->N;
   // Drones per 64-lane block.  A wave's time is set by its serial instruction stream, not by
   // how many of its lanes are active, while a CU streams the observation rows of its blocks at
   // a limited store-issue rate; so when there are too few drones to give every CU a full wave,
@@ -1224,10 +940,8 @@ int create_impl(const gpd_drone_params* params, const gpd_config* cfg, const Het
     const int NC = s->A == 4 ? 3 + s->ring_len : 12 + s->ring_len * s->A;
     s->nc_magic = (65536 + NC - 1) / NC;
     for (int t = 0; t <= kWave && !s->wide; ++t)   // (the wide kernel has no tile copy-out)
-      if ((t * s->nc_magic) >> 16 != t / NC) {
-        delete s;
-        return fail(GPD_EUNSUPPORTED, "gpd_create: observation width not supported by the tile copy-out");
-      }
+      if ((t * s->nc_magic) >> 16 != t / NC)
+        return fail(GPD_EUNSUPPORTED, fn + ": observation width not supported by the tile copy-out");
     // two-wave step (step_kernel_duo) for the plain-DYN single-drone RPM path while the launch
     // is latency-bound: up to 64K drones (<= 4 blocks per CU).  Measured on one MI355X
     // (scripts/geom_probe.py): 4096 envs 6.28 -> 5.71 us/step, 16384 envs 7.48 -> 6.49,
@@ -1266,14 +980,20 @@ int create_impl(const gpd_drone_params* params, const gpd_config* cfg, const Het
     const size_t state_bytes = (size_t)kStateComps * s->npad * (C.precision == GPD_F64 ? 8 : 4);
     if (state_bytes >= 0x7fffffffULL) s->wt &= ~2;
   }
-  if (s->tile_bytes > kLdsBytes && !s->wide) {
-    delete s;
-    return fail(GPD_EUNSUPPORTED, "gpd_create: ctrl_freq too high for drone <-> drone contact (observation tile "
+  if (s->tile_bytes > kLdsBytes && !s->wide)
+    return fail(GPD_EUNSUPPORTED, fn + ": ctrl_freq too high for drone <-> drone contact (observation tile "
                                   "exceeds 160 KiB of LDS; GPD_F_NO_DRONE_CONTACT lifts the limit)");
-  }
+  return GPD_OK;
+}
 
-  // derived constants (BaseAviary.py:117-128)
-  const gpd_drone_params& P = *params;
+// gpd_constants: the derived constants (BaseAviary.py:117-128) and the sim's shape.
+// (gpd_host_model.h's derive_row derives a het sim's env rows from the same lines but squares
+// MAX_RPM as Python's **2 does, with libm's pow, where this squares with x*x; the two can differ in
+// the last bit for user-supplied parameters, and gpd_get_constants and Consts::ge_clip are pinned
+// to this one: do not merge them)
+void derive_constants(gpd_sim* s) {
+  const gpd_drone_params& P = s->P;
+  const gpd_config& C = s->cfg;
   gpd_constants& K = s->K;
   std::memset(&K, 0, sizeof(K));
   K.gravity = 9.8 * P.m;
@@ -1294,136 +1014,347 @@ int create_impl(const gpd_drone_params* params, const gpd_config* cfg, const Het
   K.n_drones = s->N;
   K.drones_per_block = s->tpb;
   K.lanes_per_block = s->step_waves * kWave;
-  {  // truncated iff step_counter / PYB_FREQ > EPISODE_LEN_SEC  (HoverAviary.py:114)
-    long long sc = (long long)std::floor(C.episode_len_sec * C.pyb_freq);
-    if (sc < 0) sc = 0;
-    while (sc > 0 && (double)(sc - 1) / C.pyb_freq > C.episode_len_sec) --sc;
-    while (!((double)sc / C.pyb_freq > C.episode_len_sec)) ++sc;
-    K.trunc_step_counter = (int)std::min<long long>(sc, 0x7fffffff);
-  }
+  K.trunc_step_counter = trunc_step_counter(C.episode_len_sec, C.pyb_freq);
+}
 
-  // reset template: INIT_XYZS (BaseAviary.py:194-197) and the orientation the client stores
+// The reset template and the targets: INIT_XYZS / INIT_RPYS (BaseAviary.py:194-197; C's tables or
+// the default layout) through pose_tables.  One set of D poses for the sim; on a het sim one per
+// env, C's set for every env unless the per-env tables replace it.  C is the caller's config:
+// the sim's copy keeps no host pointers.
+void build_templates(gpd_sim* s, const gpd_config& C, const HetArgs* het) {
+  const gpd_drone_params& P = s->P;
+  const size_t D3 = (size_t)s->D * 3;
+  std::vector<double> xyz(D3), rpy(D3, 0.0);
+  for (int d = 0; d < s->D; ++d) {
+    xyz[d * 3 + 0] = d * 4 * P.arm;
+    xyz[d * 3 + 1] = d * 4 * P.arm;
+    xyz[d * 3 + 2] = P.collision_h / 2 - P.collision_z_offset + .1;
+  }
+  if (C.init_xyzs_host) xyz.assign(C.init_xyzs_host, C.init_xyzs_host + D3);
+  if (C.init_rpys_host) rpy.assign(C.init_rpys_host, C.init_rpys_host + D3);
   const size_t TE = s->het ? (size_t)s->E : 1;   // template / target tables: per env on a het sim
   s->init_tmpl.assign(TE * s->D * 10, 0.0);
   s->target.assign(TE * s->D * 3, 0.0);
-  if (s->het) {
-    s->epad = ((long long)s->E + 63) / 64 * 64;
-    s->het_xyz.resize((size_t)s->N * 3);
-    s->het_rpy.assign((size_t)s->N * 3, 0.0);
-    if (het->rows) s->env_rows.assign(het->rows, het->rows + s->E);
-    else s->env_rows.assign((size_t)s->E, env_row_of(P));
+  if (!s->het) {
+    pose_tables(C.task, 1, s->D, xyz.data(), rpy.data(), s->init_tmpl.data(), s->target.data());
+    return;
   }
-  for (int d = 0; d < s->D; ++d) {
-    double xyz[3], rpy[3] = {0, 0, 0};
-    if (C.init_xyzs_host) {
-      for (int k = 0; k < 3; ++k) xyz[k] = C.init_xyzs_host[d * 3 + k];
-    } else {
-      xyz[0] = d * 4 * P.arm;
-      xyz[1] = d * 4 * P.arm;
-      xyz[2] = P.collision_h / 2 - P.collision_z_offset + .1;
-    }
-    if (C.init_rpys_host)
-      for (int k = 0; k < 3; ++k) rpy[k] = C.init_rpys_host[d * 3 + k];
-    if (s->het) {   // cfg's pose for every env unless the per-env tables replace it (het_templates below)
-      for (int e = 0; e < s->E; ++e)
-        for (int k = 0; k < 3; ++k) {
-          const size_t i = ((size_t)e * s->D + d) * 3 + k;
-          s->het_xyz[i] = het->xyzs ? het->xyzs[i] : xyz[k];
-          s->het_rpy[i] = het->rpys ? het->rpys[i] : rpy[k];
-        }
-      continue;
-    }
-    pose_template(xyz, rpy, &s->init_tmpl[(size_t)d * 10]);
-    if (C.task == GPD_TASK_HOVER) {           // HoverAviary.py:51
-      s->target[d * 3 + 2] = 1.0;
-    } else if (C.task == GPD_TASK_MULTIHOVER) {  // MultiHoverAviary.py:71
-      s->target[d * 3 + 0] = xyz[0];
-      s->target[d * 3 + 1] = xyz[1];
-      s->target[d * 3 + 2] = xyz[2] + 1.0 / (d + 1);
-    }
+  s->epad = ((long long)s->E + 63) / 64 * 64;
+  if (het->rows) s->env_rows.assign(het->rows, het->rows + s->E);
+  else s->env_rows.assign((size_t)s->E, env_row_of(P));
+  s->het_xyz.resize((size_t)s->N * 3);
+  s->het_rpy.resize((size_t)s->N * 3);
+  for (int e = 0; e < s->E; ++e) {
+    std::copy_n(het->xyzs ? het->xyzs + e * D3 : xyz.data(), D3, &s->het_xyz[e * D3]);
+    std::copy_n(het->rpys ? het->rpys + e * D3 : rpy.data(), D3, &s->het_rpy[e * D3]);
   }
-  if (s->het) het_templates(s);
+  het_templates(s);
+}
 
-  const size_t rs = real_size(s);
-  hipError_t e1 = hipMalloc(&s->d_state, (size_t)kStateComps * s->npad * rs);
-  hipError_t e2 = hipMalloc((void**)&s->d_ring, (size_t)s->ring_len * s->npad * s->A * sizeof(float));
-  hipError_t e3 = hipMalloc((void**)&s->d_ctr, (size_t)(s->E + 1) * sizeof(int2));
-  hipError_t e4 = hipMalloc(&s->d_init, TE * s->D * 10 * rs);
-  hipError_t e5 = hipMalloc(&s->d_target, TE * s->D * 3 * rs);
-  hipError_t e6 = hipMalloc(&s->d_consts, s->prec == GPD_F64 ? sizeof(Consts<double>) : sizeof(Consts<float>));
-  hipError_t e7 = pid ? hipMalloc(&s->d_ctrl, (size_t)kCtrlComps * s->npad * rs) : hipSuccess;
-  hipError_t e8 = s->het ? hipMalloc(&s->d_etab, (size_t)kHetCols * s->epad * rs) : hipSuccess;
-  if (s->het && e8 == hipSuccess) e8 = hipMalloc((void**)&s->d_draws, (size_t)s->E * 3 * sizeof(int));
-  if (s->het && e8 == hipSuccess)
-    e8 = hipMalloc(&s->d_pool, s->prec == GPD_F64 ? sizeof(ResetPool<double>) : sizeof(ResetPool<float>));
-  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess ||
-      e6 != hipSuccess || e7 != hipSuccess || e8 != hipSuccess) {
-    free_sim(s);
+// hipMalloc on the create path: GPD_ENOMEM under the caller's message
+int dev_alloc(void** p, size_t bytes, const std::string& msg) {
+  if (hipMalloc(p, bytes) == hipSuccess) return GPD_OK;
+  (void)hipGetLastError();
+  return fail(GPD_ENOMEM, msg);
+}
+
+// drone <-> drone contact (gpd_dcontact.h DcHook / dc_solve): the pair table of an env and the
+// row store for a block's contacts past its first 64 (up to kDcPts per pair: the closest point
+// and the face manifold)
+int alloc_drone_contact(const std::string& fn, gpd_sim* s) {
+  const int D = s->D, P = D * (D - 1) / 2;
+  const int npairs = (s->tpb / D) * P;
+  s->dcP = P;
+  s->dc_pmagic = ((1 << 24) + P - 1) / P;   // exact for p < npairs <= 32 (D - 1) <= 2016 (p P < 2^24)
+  for (int p = 0; p < npairs; ++p)
+    if (((p * s->dc_pmagic) >> 24) != p / P)
+      return fail(GPD_EUNSUPPORTED, fn + ": drone contact pair layout not supported");
+  std::vector<int> tab;
+  tab.reserve(P);
+  for (int i = 0; i < D; ++i)
+    for (int j = i + 1; j < D; ++j) tab.push_back(i | (j << 8));   // bullet_mb.drone_contacts' order
+  int rc = dev_alloc((void**)&s->d_dc_tab, (size_t)P * sizeof(int), fn + ": drone contact pair table");
+  if (rc != GPD_OK) return rc;
+  if (hipMemcpy(s->d_dc_tab, tab.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
     (void)hipGetLastError();
-    return fail(GPD_ENOMEM, "gpd_create: hipMalloc failed");
+    return fail(GPD_ENOMEM, fn + ": drone contact pair table");
   }
-  if ((C.physics_flags & GPD_F_BULLET) && s->D > 1 && !(C.physics_flags & GPD_F_NO_DRONE_CONTACT)) {
-    // drone <-> drone contact (gpd_dcontact.h DcHook / dc_solve): the pair table of an env and the
-    // row store for a block's contacts past its first 64 (up to kDcPts per pair: the closest point
-    // and the face manifold)
-    const int D = s->D, P = D * (D - 1) / 2;
-    const int npairs = (s->tpb / D) * P;
-    s->dcP = P;
-    s->dc_pmagic = ((1 << 24) + P - 1) / P;   // exact for p < npairs <= 32 (D - 1) <= 2016 (p P < 2^24)
-    for (int p = 0; p < npairs; ++p)
-      if (((p * s->dc_pmagic) >> 24) != p / P) {
-        free_sim(s);
-        return fail(GPD_EUNSUPPORTED, "gpd_create: drone contact pair layout not supported");
-      }
-    std::vector<int> tab;
-    tab.reserve(P);
-    for (int i = 0; i < D; ++i)
-      for (int j = i + 1; j < D; ++j) tab.push_back(i | (j << 8));   // bullet_mb.drone_contacts' order
-    if (hipMalloc((void**)&s->d_dc_tab, (size_t)P * sizeof(int)) != hipSuccess ||
-        hipMemcpy(s->d_dc_tab, tab.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-      free_sim(s);
-      (void)hipGetLastError();
-      return fail(GPD_ENOMEM, "gpd_create: drone contact pair table");
-    }
-    if (npairs * kDcPts > kDcRegRows * kWave) {
-      const int row_reals = s->prec == GPD_F64 ? dc_row_reals<double>() : dc_row_reals<float>();
-      const int chunks = (npairs * kDcPts + kWave - 1) / kWave - kDcRegRows;
-      s->dc_row_stride = (long long)chunks * kWave * row_reals;
-      const long long blocks = ((long long)s->N + s->tpb - 1) / s->tpb;
-      if (hipMalloc(&s->d_dc_rows, (size_t)(blocks * s->dc_row_stride) * rs) != hipSuccess) {
-        free_sim(s);
-        (void)hipGetLastError();
-        return fail(GPD_ENOMEM, "gpd_create: drone contact row store");
-      }
-    }
+  if (npairs * kDcPts > kDcRegRows * kWave) {
+    const int row_reals = by_real(s, [](auto r) { return dc_row_reals<decltype(r)>(); });
+    const int chunks = (npairs * kDcPts + kWave - 1) / kWave - kDcRegRows;
+    s->dc_row_stride = (long long)chunks * kWave * row_reals;
+    const long long blocks = ((long long)s->N + s->tpb - 1) / s->tpb;
+    rc = dev_alloc(&s->d_dc_rows, (size_t)(blocks * s->dc_row_stride) * real_size(s), fn + ": drone contact row store");
   }
-  int rc = s->prec == GPD_F64 ? upload_tables<double>(s) : upload_tables<float>(s);
-  if (rc == GPD_OK && s->het) rc = s->prec == GPD_F64 ? upload_env_table<double>(s) : upload_env_table<float>(s);
+  return rc;
+}
+
+int alloc_device(const std::string& fn, gpd_sim* s) {
+  const std::string msg = fn + ": hipMalloc failed";
+  int rc = dev_alloc(&s->d_state, state_buf_bytes(s), msg);
+  if (rc == GPD_OK) rc = dev_alloc((void**)&s->d_ring, ring_buf_bytes(s), msg);
+  if (rc == GPD_OK) rc = dev_alloc((void**)&s->d_ctr, ctr_buf_bytes(s) + sizeof(int2), msg);
+  if (rc == GPD_OK) rc = dev_alloc(&s->d_init, tmpl_buf_bytes(s), msg);
+  if (rc == GPD_OK) rc = dev_alloc(&s->d_target, target_buf_bytes(s), msg);
+  if (rc == GPD_OK) rc = dev_alloc(&s->d_consts, by_real(s, [](auto r) { return sizeof(Consts<decltype(r)>); }), msg);
+  if (rc == GPD_OK && act_is_pid(s->cfg.act_type)) rc = dev_alloc(&s->d_ctrl, ctrl_buf_bytes(s), msg);
+  if (rc == GPD_OK && s->het) rc = dev_alloc(&s->d_etab, etab_buf_bytes(s), msg);
+  if (rc == GPD_OK && s->het) rc = dev_alloc((void**)&s->d_draws, (size_t)s->E * 3 * sizeof(int), msg);
+  if (rc == GPD_OK && s->het) rc = dev_alloc(&s->d_pool, pool_desc_bytes(s), msg);
+  const int pf = s->cfg.physics_flags;
+  if (rc == GPD_OK && (pf & GPD_F_BULLET) && s->D > 1 && !(pf & GPD_F_NO_DRONE_CONTACT)) rc = alloc_drone_contact(fn, s);
+  return rc;
+}
+
+// the tables onto the device, every buffer cleared, every env reset
+int upload_and_reset(const std::string& fn, gpd_sim* s) {
+  int rc = by_real(s, [&](auto r) { return upload_tables<decltype(r)>(s); });
+  if (rc == GPD_OK && s->het) rc = by_real(s, [&](auto r) { return upload_env_table<decltype(r)>(s); });
   if (rc == GPD_OK && s->het) {   // no pool; every env in episode 0 on its own row and pose
     std::vector<int> dr((size_t)s->E * 3, -1);
     for (int e = 0; e < s->E; ++e) dr[(size_t)e * 3] = 0;
-    if (hipMemset(s->d_pool, 0, s->prec == GPD_F64 ? sizeof(ResetPool<double>) : sizeof(ResetPool<float>)) != hipSuccess ||
+    if (hipMemset(s->d_pool, 0, pool_desc_bytes(s)) != hipSuccess ||
         hipMemcpy(s->d_draws, dr.data(), dr.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
       rc = fail(GPD_EHIP, "gpd_create_het: reset pool state");
   }
-  if (rc != GPD_OK) { free_sim(s); return rc; }
-  if (hipMemset(s->d_state, 0, (size_t)kStateComps * s->npad * rs) != hipSuccess ||
-      hipMemset(s->d_ring, 0, (size_t)s->ring_len * s->npad * s->A * sizeof(float)) != hipSuccess ||
-      hipMemset(s->d_ctr, 0, (size_t)(s->E + 1) * sizeof(int2)) != hipSuccess ||
-      (pid && hipMemset(s->d_ctrl, 0, (size_t)kCtrlComps * s->npad * rs) != hipSuccess)) {
-    free_sim(s);
-    return fail(GPD_EHIP, "gpd_create: hipMemset failed");
+  if (rc != GPD_OK) return rc;
+  if (hipMemset(s->d_state, 0, state_buf_bytes(s)) != hipSuccess ||
+      hipMemset(s->d_ring, 0, ring_buf_bytes(s)) != hipSuccess ||
+      hipMemset(s->d_ctr, 0, ctr_buf_bytes(s) + sizeof(int2)) != hipSuccess ||
+      (s->d_ctrl && hipMemset(s->d_ctrl, 0, ctrl_buf_bytes(s)) != hipSuccess))
+    return fail(GPD_EHIP, fn + ": hipMemset failed");
+  rc = by_real(s, [&](auto r) { return launch_reset<decltype(r)>(s, nullptr, nullptr, 0); });
+  if (rc == GPD_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(GPD_EHIP, fn + ": initial reset failed");
+  return rc;
+}
+
+// gpd_create (het null) and gpd_create_het, which has checked what only a het sim needs
+int create_impl(const std::string& fn, const gpd_drone_params* params, const gpd_config* cfg, const HetArgs* het,
+                gpd_sim** out) {
+  if (!params || !cfg || !out) return fail(GPD_EINVAL, fn + ": NULL argument");
+  *out = nullptr;
+  int rc = validate_config(fn, params, *cfg);
+  if (rc != GPD_OK) return rc;
+  SimPtr s = new_sim(params, *cfg, het != nullptr);
+  rc = plan_launch(fn, s.get());
+  if (rc != GPD_OK) return rc;
+  derive_constants(s.get());
+  build_templates(s.get(), *cfg, het);
+  rc = alloc_device(fn, s.get());
+  if (rc == GPD_OK) rc = upload_and_reset(fn, s.get());
+  if (rc != GPD_OK) return rc;
+  *out = s.release();
+  return GPD_OK;
+}
+
+// gpd_set_pid_gains: the [N][18] table rounded once to the sim's real type, tiled [npad/64][18][64]
+// (padding drones: zeros, never read)
+template <typename R>
+int install_gains(gpd_sim* sim, const double* gains) {
+  const size_t N = (size_t)sim->N;
+  std::vector<double> stored(N * kGainComps);
+  std::vector<R> tiled((size_t)kGainComps * (size_t)sim->npad, R(0));
+  for (size_t n = 0; n < N; ++n)
+    for (int k = 0; k < kGainComps; ++k) {
+      const R x = (R)gains[n * kGainComps + k];
+      tiled[(size_t)tidx((long long)n, k, kGainComps)] = x;
+      stored[n * kGainComps + k] = (double)x;
+      if (!std::isfinite(x))   // a finite double past float's range rounds to infinity
+        return fail(GPD_EINVAL, "gpd_set_pid_gains: non-finite value in row " + std::to_string(n) + ", column " +
+                                    std::to_string(k) + " (out of float32 range)");
+    }
+  const size_t bytes = tiled.size() * sizeof(R);
+  HIP_TRY(hipDeviceSynchronize());
+  if (!sim->d_gains && hipMalloc(&sim->d_gains, bytes) != hipSuccess) {
+    sim->d_gains = nullptr;
+    return fail(GPD_ENOMEM, "gpd_set_pid_gains: device allocation of the gain table failed");
   }
-  rc = s->prec == GPD_F64 ? launch_reset<double>(s, nullptr, nullptr, 0) : launch_reset<float>(s, nullptr, nullptr, 0);
-  if (rc == GPD_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(GPD_EHIP, "gpd_create: initial reset failed");
-  if (rc != GPD_OK) { free_sim(s); return rc; }
-  *out = s;
+  HIP_TRY(hipMemcpy(sim->d_gains, tiled.data(), bytes, hipMemcpyHostToDevice));
+  sim->gains.swap(stored);
+  sim->gains_on = true;
+  return GPD_OK;
+}
+
+// ---- argument checks shared by paired entry points; fn is the entry point's name.  The order of
+// the checks is part of the interface: callers see the first failure.
+int need_het(const char* fn, const gpd_sim* sim) {
+  if (sim->het) return GPD_OK;
+  return fail(GPD_EINVAL, std::string(fn) + ": not a het sim (create it with gpd_create_het)");
+}
+
+// gpd_step and gpd_step_seq (gpd_step: one slot)
+int check_step_args(const char* fn, const gpd_sim* sim, const float* actions, const float* obs, const float* reward,
+                    const uint8_t* terminated, const uint8_t* truncated, const float* terminal_obs, int n_slots = 1,
+                    int n_steps = 0) {
+  const auto err = [fn](int code, const std::string& what) { return fail(code, std::string(fn) + what); };
+  if (!sim || !actions || !obs || !reward || !terminated || !truncated)
+    return err(GPD_EINVAL, ": NULL argument");
+  if (n_slots < 1 || n_steps < 0) return err(GPD_EINVAL, ": n_slots must be >= 1, n_steps >= 0");
+  if (sim->A == 4 && !aligned16(actions)) return err(GPD_EINVAL, ": actions must be 16-byte aligned");
+  if (sim->A == 4 && (!aligned16(obs) || (terminal_obs && !aligned16(terminal_obs))))
+    return err(GPD_EINVAL, ": obs buffers must be 16-byte aligned");
+  if (sim->gains_on)
+    return err(GPD_EUNSUPPORTED, ": a per-drone gain table is in force (gpd_set_pid_gains) and the RL step "
+                                 "reads the sim-wide coefficients; clear the table with gpd_set_pid_gains(sim, NULL)");
+  return GPD_OK;
+}
+
+// gpd_cmd_step and gpd_cmd_rollout (gpd_cmd_step: a rollout of one step that records nothing)
+int check_cmd_args(const char* fn, const gpd_sim* sim, int mode, const void* actions, const void* obs20,
+                   int n_steps = 1, int record_every = 1, int max_steps_per_launch = 0, const void* traj = nullptr,
+                   const void* metrics = nullptr) {
+  const auto err = [fn](int code, const std::string& what) { return fail(code, std::string(fn) + what); };
+  if (mode != GPD_CMD_RPM && mode != GPD_CMD_VEL && mode != GPD_CMD_WAYPOINT)
+    return err(GPD_EINVAL, ": unknown mode " + std::to_string(mode) +
+                           " (GPD_CMD_RPM, GPD_CMD_VEL or GPD_CMD_WAYPOINT)");
+  if (n_steps < 0) return err(GPD_EINVAL, ": n_steps < 0");
+  if (record_every < 1) return err(GPD_EINVAL, ": record_every must be >= 1");
+  if (max_steps_per_launch < 0)
+    return err(GPD_EINVAL, ": max_steps_per_launch must be 0 (the default, 256) or >= 1");
+  if (!sim) return err(GPD_EINVAL, ": NULL sim");
+  if (n_steps > 0 && !actions) return err(GPD_EINVAL, ": NULL actions");
+  if (sim->het)
+    return err(GPD_EUNSUPPORTED, ": not supported on a het sim (the command step kernels read the "
+                                 "sim-wide drone parameters)");
+  if (mode != GPD_CMD_RPM && !sim->d_ctrl)
+    return err(GPD_EINVAL, ": the VEL and WAYPOINT modes run DSLPIDControl, and the sim's action type "
+                           "has no controller (create it with a PID action type)");
+  if (metrics && mode != GPD_CMD_WAYPOINT)
+    return err(GPD_EINVAL, ": metrics needs GPD_CMD_WAYPOINT (the tracking error is measured "
+                           "against the waypoint rows' target positions)");
+  // RPM and VEL rows are loaded as 16-byte vectors, the state20 rows stored as such
+  if (mode != GPD_CMD_WAYPOINT && actions && !aligned16(actions))
+    return err(GPD_EINVAL, ": actions must be 16-byte aligned");
+  if (traj && !aligned16(traj)) return err(GPD_EINVAL, ": traj must be 16-byte aligned");
+  if (obs20 && !aligned16(obs20)) return err(GPD_EINVAL, ": obs20 must be 16-byte aligned");
+  if (metrics && !aligned16(metrics)) return err(GPD_EINVAL, ": metrics must be 16-byte aligned");
   return GPD_OK;
 }
 
 }  // namespace
 
 extern "C" {
+
+int gpd_abi_version(void) { return GPD_ABI_VERSION; }
+
+const char* gpd_last_error(void) { return g_err.c_str(); }
+
+int gpd_default_params(int model, gpd_drone_params* out) { return default_params(model, out); }
+
+int gpd_create(const gpd_drone_params* params, const gpd_config* cfg, gpd_sim** out) {
+  return create_impl("gpd_create", params, cfg, nullptr, out);
+}
+
+int gpd_create_het(const gpd_drone_params* params, const gpd_config* cfg, const gpd_env_params* env_params_host,
+                   const double* init_xyzs_host, const double* init_rpys_host, gpd_sim** out) {
+  if (!params || !cfg || !out) return fail(GPD_EINVAL, "gpd_create_het: NULL argument");
+  *out = nullptr;
+  const gpd_config& C = *cfg;
+  // what a het sim supports, then every row and pose: all before the first device call
+  if (C.n_envs < 1) return fail(GPD_EINVAL, "gpd_create_het: n_envs must be >= 1");
+  if (C.drones_per_env < 1) return fail(GPD_EINVAL, "gpd_create_het: drones_per_env must be >= 1");
+  if (C.physics_flags & GPD_F_BULLET)
+    return fail(GPD_EUNSUPPORTED, "gpd_create_het: GPD_F_BULLET (Physics.PYB*) is not supported with per-env "
+                                  "parameters: the contact solves hold mass and inertia in derived rows; use the DYN "
+                                  "integrator (Physics.DYN)");
+  if (C.physics_flags & ~kHetFlags) return fail(GPD_EINVAL, "gpd_create_het: unknown or contact-only physics flag");
+  if (C.act_type != GPD_ACT_RPM && C.act_type != GPD_ACT_ONE_D_RPM)
+    return fail(GPD_EUNSUPPORTED, "gpd_create_het: the PID action types are not supported with per-env parameters "
+                                  "(DSLPIDControl is tuned for the nominal drone); use GPD_ACT_RPM or GPD_ACT_ONE_D_RPM");
+  if (C.drones_per_env > kWave)
+    return fail(GPD_EUNSUPPORTED, "gpd_create_het: drones_per_env > 64 needs the multi-wave step kernel, which has no "
+                                  "per-env parameters");
+  if (C.ctrl_freq >= 2 &&
+      (size_t)step_tile_bytes(act_width(C.act_type), C.ctrl_freq / 2) + kHetStaticLds > kLdsBytes)
+    return fail(GPD_EUNSUPPORTED, "gpd_create_het: the action history (ctrl_freq // 2 slots) does not fit the one-wave "
+                                  "step kernel's observation tile; the multi-wave kernel has no per-env parameters");
+  const long long N = (long long)C.n_envs * C.drones_per_env;
+  int rc = env_params_host ? check_env_rows("gpd_create_het", env_params_host, C.n_envs) : GPD_OK;
+  if (rc == GPD_OK) rc = check_poses("gpd_create_het", "init_xyzs", init_xyzs_host, N, C.drones_per_env);
+  if (rc == GPD_OK) rc = check_poses("gpd_create_het", "init_rpys", init_rpys_host, N, C.drones_per_env);
+  if (rc != GPD_OK) return rc;
+  const HetArgs het{env_params_host, init_xyzs_host, init_rpys_host};
+  return create_impl("gpd_create_het", params, cfg, &het, out);   // the shared checks under this entry point's name
+}
+
+int gpd_set_env_params(gpd_sim* sim, const gpd_env_params* rows_host) {
+  if (!sim || !rows_host) return fail(GPD_EINVAL, "gpd_set_env_params: NULL argument");
+  if (need_het("gpd_set_env_params", sim) != GPD_OK) return GPD_EINVAL;
+  int rc = check_env_rows("gpd_set_env_params", rows_host, sim->E);
+  if (rc != GPD_OK) return rc;
+  // a last action still in the ring (store-policy bit 2) is rebuilt from the env's hover column:
+  // settle it with the rows the steps ran on, before they are replaced
+  rc = settle_last_any(sim, 0);
+  if (rc != GPD_OK) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  rc = fold_draws(sim, 1);   // every row index back to -1: the rows in force are the new ones
+  if (rc != GPD_OK) return rc;
+  sim->env_rows.assign(rows_host, rows_host + sim->E);
+  return by_real(sim, [&](auto r) { return upload_env_table<decltype(r)>(sim); });
+}
+
+int gpd_set_env_init(gpd_sim* sim, const double* xyzs_host, const double* rpys_host) {
+  if (!sim) return fail(GPD_EINVAL, "gpd_set_env_init: NULL sim");
+  if (need_het("gpd_set_env_init", sim) != GPD_OK) return GPD_EINVAL;
+  int rc = check_poses("gpd_set_env_init", "init_xyzs", xyzs_host, sim->N, sim->D);
+  if (rc == GPD_OK) rc = check_poses("gpd_set_env_init", "init_rpys", rpys_host, sim->N, sim->D);
+  if (rc != GPD_OK) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  rc = fold_draws(sim, 2);   // a NULL table keeps the poses in force; every pose index back to -1
+  if (rc != GPD_OK) return rc;
+  if (xyzs_host) sim->het_xyz.assign(xyzs_host, xyzs_host + (size_t)sim->N * 3);
+  if (rpys_host) sim->het_rpy.assign(rpys_host, rpys_host + (size_t)sim->N * 3);
+  het_templates(sim);
+  return by_real(sim, [&](auto r) { return upload_tables<decltype(r)>(sim); });
+}
+
+int gpd_env_derive(const gpd_drone_params* base, const gpd_env_params* rows, int n, gpd_constants* out) {
+  if (!base || !rows || !out || n < 0) return fail(GPD_EINVAL, "gpd_env_derive: NULL argument or n < 0");
+  for (int i = 0; i < n; ++i) derive_row(*base, rows[i], out[i]);
+  return GPD_OK;
+}
+
+int gpd_reset_pool_draw(unsigned seed, int stream, long long env, int episode, int n) {
+  if (n < 1) return 0;
+  return pool_draw(seed, (unsigned)stream, (unsigned)env, (unsigned)episode, (unsigned)n);
+}
+
+int gpd_set_reset_pool(gpd_sim* sim, const gpd_env_params* rows_host, int n_rows, const double* xyzs_host,
+                       const double* rpys_host, int n_poses, unsigned seed) {
+  if (!sim) return fail(GPD_EINVAL, "gpd_set_reset_pool: NULL sim");
+  if (need_het("gpd_set_reset_pool", sim) != GPD_OK) return GPD_EINVAL;
+  if (n_rows < 0 || n_poses < 0) return fail(GPD_EINVAL, "gpd_set_reset_pool: n_rows and n_poses must be >= 0");
+  if (n_rows > 0 && !rows_host) return fail(GPD_EINVAL, "gpd_set_reset_pool: rows_host is NULL but n_rows > 0");
+  if (n_poses > 0 && !xyzs_host) return fail(GPD_EINVAL, "gpd_set_reset_pool: xyzs_host is NULL but n_poses > 0");
+  const long long nq = (long long)n_poses * sim->D;
+  int rc = check_env_rows("gpd_set_reset_pool", rows_host, n_rows, "pool row");
+  if (rc == GPD_OK) rc = check_poses("gpd_set_reset_pool", "xyzs", n_poses ? xyzs_host : nullptr, nq, sim->D, "pool pose");
+  if (rc == GPD_OK) rc = check_poses("gpd_set_reset_pool", "rpys", n_poses ? rpys_host : nullptr, nq, sim->D, "pool pose");
+  if (rc != GPD_OK) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  rc = fold_draws(sim, 3);   // what the old pools gave stays in force, as the env's own
+  if (rc != GPD_OK) return rc;
+  sim->pool_rows.assign(rows_host, rows_host + n_rows);
+  sim->pool_xyz.assign(xyzs_host, xyzs_host + nq * 3);
+  if (n_poses && rpys_host) sim->pool_rpy.assign(rpys_host, rpys_host + nq * 3);
+  else sim->pool_rpy.assign((size_t)nq * 3, 0.0);
+  return by_real(sim, [&](auto r) { return upload_pool<decltype(r)>(sim, seed); });
+}
+
+int gpd_get_reset_draws(gpd_sim* sim, int* out_dev, void* stream) {
+  if (!sim || !out_dev) return fail(GPD_EINVAL, "gpd_get_reset_draws: NULL argument");
+  if (need_het("gpd_get_reset_draws", sim) != GPD_OK) return GPD_EINVAL;
+  HIP_TRY(hipMemcpyAsync(out_dev, sim->d_draws, (size_t)sim->E * 3 * sizeof(int), hipMemcpyDeviceToDevice,
+                         (hipStream_t)stream));
+  return GPD_OK;
+}
+
+int gpd_get_env_table(gpd_sim* sim, double* out_host) {
+  if (!sim || !out_host) return fail(GPD_EINVAL, "gpd_get_env_table: NULL argument");
+  if (need_het("gpd_get_env_table", sim) != GPD_OK) return GPD_EINVAL;
+  HIP_TRY(hipDeviceSynchronize());
+  return by_real(sim, [&](auto r) { return env_table_to_host<decltype(r)>(sim, out_host); });
+}
 
 int gpd_destroy(gpd_sim* sim) {
   if (!sim) return fail(GPD_EINVAL, "gpd_destroy: NULL sim");
@@ -1440,163 +1371,90 @@ int gpd_get_constants(const gpd_sim* sim, gpd_constants* out) {
 
 int gpd_reset(gpd_sim* sim, const uint8_t* env_mask, float* obs, void* stream) {
   if (!sim) return fail(GPD_EINVAL, "gpd_reset: NULL sim");
-  hipStream_t st = (hipStream_t)stream;
-  return sim->prec == GPD_F64 ? launch_reset<double>(sim, env_mask, obs, st) : launch_reset<float>(sim, env_mask, obs, st);
+  return by_real(sim, [&](auto r) { return launch_reset<decltype(r)>(sim, env_mask, obs, (hipStream_t)stream); });
 }
 
 int gpd_step(gpd_sim* sim, const float* actions, float* obs, float* reward, uint8_t* terminated,
              uint8_t* truncated, float* terminal_obs, void* stream) {
-  if (!sim || !actions || !obs || !reward || !terminated || !truncated)
-    return fail(GPD_EINVAL, "gpd_step: NULL argument");
-  if (sim->A == 4 && !aligned16(actions)) return fail(GPD_EINVAL, "gpd_step: actions must be 16-byte aligned");
-  if (sim->A == 4 && (!aligned16(obs) || (terminal_obs && !aligned16(terminal_obs))))
-    return fail(GPD_EINVAL, "gpd_step: obs buffers must be 16-byte aligned");
-  if (sim->gains_on)
-    return fail(GPD_EUNSUPPORTED, "gpd_step: a per-drone gain table is in force (gpd_set_pid_gains) and the RL step "
-                                  "reads the sim-wide coefficients; clear the table with gpd_set_pid_gains(sim, NULL)");
+  const int rc = check_step_args("gpd_step", sim, actions, obs, reward, terminated, truncated, terminal_obs);
+  if (rc != GPD_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  return sim->prec == GPD_F64
-             ? launch_step<double>(sim, actions, obs, reward, terminated, truncated, terminal_obs, st)
-             : launch_step<float>(sim, actions, obs, reward, terminated, truncated, terminal_obs, st);
+  return by_real(sim, [&](auto r) {
+    return launch_step<decltype(r)>(sim, actions, obs, reward, terminated, truncated, terminal_obs, st);
+  });
 }
 
 int gpd_step_seq(gpd_sim* sim, const float* actions, int n_slots, int n_steps, float* obs, float* reward,
                  uint8_t* terminated, uint8_t* truncated, float* terminal_obs, void* stream) {
-  if (!sim || !actions || !obs || !reward || !terminated || !truncated)
-    return fail(GPD_EINVAL, "gpd_step_seq: NULL argument");
-  if (n_slots < 1 || n_steps < 0) return fail(GPD_EINVAL, "gpd_step_seq: n_slots must be >= 1, n_steps >= 0");
-  if (sim->A == 4 && !aligned16(actions)) return fail(GPD_EINVAL, "gpd_step_seq: actions must be 16-byte aligned");
-  if (sim->A == 4 && (!aligned16(obs) || (terminal_obs && !aligned16(terminal_obs))))
-    return fail(GPD_EINVAL, "gpd_step_seq: obs buffers must be 16-byte aligned");
-  if (sim->gains_on)
-    return fail(GPD_EUNSUPPORTED, "gpd_step_seq: a per-drone gain table is in force (gpd_set_pid_gains) and the RL step "
-                                  "reads the sim-wide coefficients; clear the table with gpd_set_pid_gains(sim, NULL)");
+  const int rc = check_step_args("gpd_step_seq", sim, actions, obs, reward, terminated, truncated, terminal_obs, n_slots,
+                                 n_steps);
+  if (rc != GPD_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   const size_t slot = (size_t)sim->N * sim->A;
-  for (int t = 0; t < n_steps; ++t) {
-    const float* a = actions + (size_t)(t % n_slots) * slot;
-    const int rc = sim->prec == GPD_F64
-                       ? launch_step<double>(sim, a, obs, reward, terminated, truncated, terminal_obs, st)
-                       : launch_step<float>(sim, a, obs, reward, terminated, truncated, terminal_obs, st);
-    if (rc != GPD_OK) return rc;
-  }
-  return GPD_OK;
+  return by_real(sim, [&](auto r) {
+    for (int t = 0; t < n_steps; ++t) {
+      const float* a = actions + (size_t)(t % n_slots) * slot;
+      const int rc = launch_step<decltype(r)>(sim, a, obs, reward, terminated, truncated, terminal_obs, st);
+      if (rc != GPD_OK) return rc;
+    }
+    return (int)GPD_OK;
+  });
 }
 
 int gpd_integrate(gpd_sim* sim, const void* rpm, int n_sub, void* traj, void* stream) {
   if (!sim || !rpm) return fail(GPD_EINVAL, "gpd_integrate: NULL argument");
   if (n_sub < 0) return fail(GPD_EINVAL, "gpd_integrate: n_sub < 0");
   if (n_sub == 0) return GPD_OK;
-  hipStream_t st = (hipStream_t)stream;
-  return sim->prec == GPD_F64 ? launch_integrate<double>(sim, rpm, n_sub, traj, st)
-                              : launch_integrate<float>(sim, rpm, n_sub, traj, st);
+  return by_real(sim, [&](auto r) { return launch_integrate<decltype(r)>(sim, rpm, n_sub, traj, (hipStream_t)stream); });
 }
 
 int gpd_cmd_step(gpd_sim* sim, int mode, const void* actions, void* obs20, void* stream) {
-  if (mode != GPD_CMD_RPM && mode != GPD_CMD_VEL && mode != GPD_CMD_WAYPOINT)
-    return fail(GPD_EINVAL, "gpd_cmd_step: unknown mode " + std::to_string(mode) +
-                                " (GPD_CMD_RPM, GPD_CMD_VEL or GPD_CMD_WAYPOINT)");
-  if (!sim) return fail(GPD_EINVAL, "gpd_cmd_step: NULL sim");
-  if (!actions) return fail(GPD_EINVAL, "gpd_cmd_step: NULL actions");
-  if (sim->het)
-    return fail(GPD_EUNSUPPORTED, "gpd_cmd_step: not supported on a het sim (the command step kernels read the "
-                                  "sim-wide drone parameters)");
-  if (mode != GPD_CMD_RPM && !sim->d_ctrl)
-    return fail(GPD_EINVAL, "gpd_cmd_step: the VEL and WAYPOINT modes run DSLPIDControl, and the sim's action type "
-                            "has no controller (create it with a PID action type)");
-  // RPM and VEL rows are loaded as 16-byte vectors, the state20 rows stored as such
-  if (mode != GPD_CMD_WAYPOINT && !aligned16(actions))
-    return fail(GPD_EINVAL, "gpd_cmd_step: actions must be 16-byte aligned");
-  if (obs20 && !aligned16(obs20)) return fail(GPD_EINVAL, "gpd_cmd_step: obs20 must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  return sim->prec == GPD_F64 ? launch_cmd_step<double>(sim, mode, actions, obs20, st)
-                              : launch_cmd_step<float>(sim, mode, actions, obs20, st);
+  const int rc = check_cmd_args("gpd_cmd_step", sim, mode, actions, obs20);
+  if (rc != GPD_OK) return rc;
+  return by_real(sim, [&](auto r) { return launch_cmd_step<decltype(r)>(sim, mode, actions, obs20, (hipStream_t)stream); });
 }
 
 int gpd_cmd_rollout(gpd_sim* sim, int mode, const void* actions, int n_steps, int record_every, void* traj,
                     void* obs20, void* metrics, int max_steps_per_launch, void* stream) {
-  if (mode != GPD_CMD_RPM && mode != GPD_CMD_VEL && mode != GPD_CMD_WAYPOINT)
-    return fail(GPD_EINVAL, "gpd_cmd_rollout: unknown mode " + std::to_string(mode) +
-                                " (GPD_CMD_RPM, GPD_CMD_VEL or GPD_CMD_WAYPOINT)");
-  if (n_steps < 0) return fail(GPD_EINVAL, "gpd_cmd_rollout: n_steps < 0");
-  if (record_every < 1) return fail(GPD_EINVAL, "gpd_cmd_rollout: record_every must be >= 1");
-  if (max_steps_per_launch < 0)
-    return fail(GPD_EINVAL, "gpd_cmd_rollout: max_steps_per_launch must be 0 (the default, 256) or >= 1");
-  if (!sim) return fail(GPD_EINVAL, "gpd_cmd_rollout: NULL sim");
-  if (n_steps > 0 && !actions) return fail(GPD_EINVAL, "gpd_cmd_rollout: NULL actions");
-  if (sim->het)
-    return fail(GPD_EUNSUPPORTED, "gpd_cmd_rollout: not supported on a het sim (the command step kernels read the "
-                                  "sim-wide drone parameters)");
-  if (mode != GPD_CMD_RPM && !sim->d_ctrl)
-    return fail(GPD_EINVAL, "gpd_cmd_rollout: the VEL and WAYPOINT modes run DSLPIDControl, and the sim's action "
-                            "type has no controller (create it with a PID action type)");
-  if (metrics && mode != GPD_CMD_WAYPOINT)
-    return fail(GPD_EINVAL, "gpd_cmd_rollout: metrics needs GPD_CMD_WAYPOINT (the tracking error is measured "
-                            "against the waypoint rows' target positions)");
-  if (mode != GPD_CMD_WAYPOINT && actions && !aligned16(actions))
-    return fail(GPD_EINVAL, "gpd_cmd_rollout: actions must be 16-byte aligned");
-  if (traj && !aligned16(traj)) return fail(GPD_EINVAL, "gpd_cmd_rollout: traj must be 16-byte aligned");
-  if (obs20 && !aligned16(obs20)) return fail(GPD_EINVAL, "gpd_cmd_rollout: obs20 must be 16-byte aligned");
-  if (metrics && !aligned16(metrics)) return fail(GPD_EINVAL, "gpd_cmd_rollout: metrics must be 16-byte aligned");
+  const int rc = check_cmd_args("gpd_cmd_rollout", sim, mode, actions, obs20, n_steps, record_every,
+                                max_steps_per_launch, traj, metrics);
+  if (rc != GPD_OK) return rc;
   if (n_steps == 0) return GPD_OK;
   const int chunk = max_steps_per_launch == 0 ? 256 : max_steps_per_launch;
   hipStream_t st = (hipStream_t)stream;
-  return sim->prec == GPD_F64
-             ? launch_cmd_rollout<double>(sim, mode, actions, n_steps, record_every, traj, obs20, metrics, chunk, st)
-             : launch_cmd_rollout<float>(sim, mode, actions, n_steps, record_every, traj, obs20, metrics, chunk, st);
+  return by_real(sim, [&](auto r) {
+    return launch_cmd_rollout<decltype(r)>(sim, mode, actions, n_steps, record_every, traj, obs20, metrics, chunk, st);
+  });
 }
 
 int gpd_adjacency(gpd_sim* sim, double radius, uint8_t* out, void* stream) {
   if (!sim) return fail(GPD_EINVAL, "gpd_adjacency: NULL sim");
   if (!out) return fail(GPD_EINVAL, "gpd_adjacency: NULL out");
   if (std::isnan(radius)) return fail(GPD_EINVAL, "gpd_adjacency: radius is NaN");
-  hipStream_t st = (hipStream_t)stream;
-  return sim->prec == GPD_F64 ? launch_adjacency<double>(sim, radius, out, st)
-                              : launch_adjacency<float>(sim, radius, out, st);
+  return by_real(sim, [&](auto r) { return launch_adjacency<decltype(r)>(sim, radius, out, (hipStream_t)stream); });
 }
 
 int gpd_get_state20(gpd_sim* sim, void* out, void* stream) {
   if (!sim || !out) return fail(GPD_EINVAL, "gpd_get_state20: NULL argument");
-  hipStream_t st = (hipStream_t)stream;
-  return sim->prec == GPD_F64 ? launch_state20<double>(sim, out, 0, st) : launch_state20<float>(sim, out, 0, st);
+  return by_real(sim, [&](auto r) { return launch_state20<decltype(r)>(sim, out, 0, (hipStream_t)stream); });
 }
 
 int gpd_get_raw_state(gpd_sim* sim, void* out, void* stream) {
   if (!sim || !out) return fail(GPD_EINVAL, "gpd_get_raw_state: NULL argument");
-  hipStream_t st = (hipStream_t)stream;
-  return sim->prec == GPD_F64 ? launch_state20<double>(sim, out, 1, st) : launch_state20<float>(sim, out, 1, st);
+  return by_real(sim, [&](auto r) { return launch_state20<decltype(r)>(sim, out, 1, (hipStream_t)stream); });
 }
 
 int gpd_nonfinite(gpd_sim* sim, uint8_t* env_flags, void* stream) {
   if (!sim || !env_flags) return fail(GPD_EINVAL, "gpd_nonfinite: NULL argument");
-  hipStream_t st = (hipStream_t)stream;
-  return sim->prec == GPD_F64 ? launch_nonfinite<double>(sim, env_flags, st) : launch_nonfinite<float>(sim, env_flags, st);
+  return by_real(sim, [&](auto r) { return launch_nonfinite<decltype(r)>(sim, env_flags, (hipStream_t)stream); });
 }
 
 int gpd_set_raw_state(gpd_sim* sim, const void* in, void* stream) {
   if (!sim || !in) return fail(GPD_EINVAL, "gpd_set_raw_state: NULL argument");
-  hipStream_t st = (hipStream_t)stream;
-  return sim->prec == GPD_F64 ? launch_set_raw<double>(sim, in, st) : launch_set_raw<float>(sim, in, st);
+  return by_real(sim, [&](auto r) { return launch_set_raw<decltype(r)>(sim, in, (hipStream_t)stream); });
 }
 
-int gpd_default_pid_params(gpd_pid_params* out) {
-  if (!out) return fail(GPD_EINVAL, "gpd_default_pid_params: out is NULL");
-  gpd_pid_params q;
-  std::memset(&q, 0, sizeof(q));
-  const double pf[3] = {.4, .4, 1.25}, iff[3] = {.05, .05, .05}, df[3] = {.2, .2, .5};       // :37-39
-  const double pt[3] = {70000., 70000., 60000.}, it[3] = {.0, .0, 500.}, dtq[3] = {20000., 20000., 12000.};  // :40-42
-  const double mix[4][3] = {{-.5, -.5, -1}, {-.5, .5, 1}, {.5, .5, -1}, {.5, -.5, 1}};     // :48-53 (CF2X)
-  for (int i = 0; i < 3; ++i) {
-    q.p_coeff_for[i] = pf[i]; q.i_coeff_for[i] = iff[i]; q.d_coeff_for[i] = df[i];
-    q.p_coeff_tor[i] = pt[i]; q.i_coeff_tor[i] = it[i]; q.d_coeff_tor[i] = dtq[i];
-  }
-  q.pwm2rpm_scale = 0.2685; q.pwm2rpm_const = 4070.3; q.min_pwm = 20000; q.max_pwm = 65535;  // :43-46
-  std::memcpy(q.mixer, mix, sizeof(mix));
-  q.gravity = 9.8 * 0.027;  // g * m of cf2x.urdf:11 (BaseControl.py:35)
-  q.kf = 3.16e-10;          // cf2x.urdf:5 (BaseControl.py:37)
-  *out = q;
-  return GPD_OK;
-}
+int gpd_default_pid_params(gpd_pid_params* out) { return default_pid_params(out); }
 
 int gpd_set_pid_params(gpd_sim* sim, const gpd_pid_params* params) {
   if (!sim || !params) return fail(GPD_EINVAL, "gpd_set_pid_params: NULL argument");
@@ -1604,7 +1462,7 @@ int gpd_set_pid_params(gpd_sim* sim, const gpd_pid_params* params) {
     return fail(GPD_EINVAL, "gpd_set_pid_params: the sim's action type has no controller");
   sim->pid = *params;
   HIP_TRY(hipDeviceSynchronize());
-  return sim->prec == GPD_F64 ? upload_tables<double>(sim) : upload_tables<float>(sim);
+  return by_real(sim, [&](auto r) { return upload_tables<decltype(r)>(sim); });
 }
 
 int gpd_set_pid_gains(gpd_sim* sim, const double* gains) {
@@ -1621,39 +1479,7 @@ int gpd_set_pid_gains(gpd_sim* sim, const double* gains) {
       if (!std::isfinite(gains[n * kGainComps + k]))
         return fail(GPD_EINVAL, "gpd_set_pid_gains: non-finite value in row " + std::to_string(n) + ", column " +
                                     std::to_string(k));
-  // rounded once to the sim's real type, tiled [npad/64][18][64] (padding drones: zeros, never read)
-  const bool f64 = sim->prec == GPD_F64;
-  const size_t count = (size_t)kGainComps * (size_t)sim->npad;
-  std::vector<double> stored(N * kGainComps);
-  std::vector<double> t64(f64 ? count : 0, 0.0);
-  std::vector<float> t32(f64 ? 0 : count, 0.0f);
-  for (size_t n = 0; n < N; ++n)
-    for (int k = 0; k < kGainComps; ++k) {
-      const double x = gains[n * kGainComps + k];
-      const size_t at = (size_t)tidx((long long)n, k, kGainComps);
-      if (f64) {
-        t64[at] = x;
-        stored[n * kGainComps + k] = x;
-      } else {
-        t32[at] = (float)x;
-        stored[n * kGainComps + k] = (double)t32[at];
-      }
-    }
-  if (!f64)   // a finite double past float's range rounds to infinity
-    for (size_t i = 0; i < stored.size(); ++i)
-      if (!std::isfinite(stored[i]))
-        return fail(GPD_EINVAL, "gpd_set_pid_gains: non-finite value in row " + std::to_string(i / kGainComps) +
-                                    ", column " + std::to_string(i % kGainComps) + " (out of float32 range)");
-  const size_t bytes = count * (f64 ? sizeof(double) : sizeof(float));
-  HIP_TRY(hipDeviceSynchronize());
-  if (!sim->d_gains && hipMalloc(&sim->d_gains, bytes) != hipSuccess) {
-    sim->d_gains = nullptr;
-    return fail(GPD_ENOMEM, "gpd_set_pid_gains: device allocation of the gain table failed");
-  }
-  HIP_TRY(hipMemcpy(sim->d_gains, f64 ? (const void*)t64.data() : (const void*)t32.data(), bytes, hipMemcpyHostToDevice));
-  sim->gains.swap(stored);
-  sim->gains_on = true;
-  return GPD_OK;
+  return by_real(sim, [&](auto r) { return install_gains<decltype(r)>(sim, gains); });
 }
 
 int gpd_get_pid_gains(gpd_sim* sim, double* out) {
@@ -1671,7 +1497,7 @@ int gpd_get_pid_gains(gpd_sim* sim, double* out) {
   double row[kGainComps];
   for (int k = 0; k < kGainComps; ++k) {
     const double x = tri[k / 3][k % 3];
-    row[k] = sim->prec == GPD_F64 ? x : (double)(float)x;
+    row[k] = by_real(sim, [&](auto r) { return (double)(decltype(r))x; });
   }
   for (size_t n = 0; n < N; ++n) std::memcpy(out + n * kGainComps, row, sizeof(row));
   return GPD_OK;
@@ -1682,12 +1508,11 @@ int gpd_get_ctrl_state(gpd_sim* sim, void* out, void* stream) {
   if (!sim->d_ctrl) return fail(GPD_EINVAL, "gpd_get_ctrl_state: the sim's action type has no controller");
   const unsigned g = grid_for(sim->N, 256);
   hipStream_t st = (hipStream_t)stream;
-  if (sim->prec == GPD_F64)
-    hipLaunchKernelGGL((soa_to_rows_kernel<double>), dim3(g), dim3(256), 0, st, (const double*)sim->d_ctrl, sim->npad,
-                       kCtrlComps, sim->N, (double*)out);
-  else
-    hipLaunchKernelGGL((soa_to_rows_kernel<float>), dim3(g), dim3(256), 0, st, (const float*)sim->d_ctrl, sim->npad,
-                       kCtrlComps, sim->N, (float*)out);
+  by_real(sim, [&](auto r) {
+    using R = decltype(r);
+    hipLaunchKernelGGL((soa_to_rows_kernel<R>), dim3(g), dim3(256), 0, st, (const R*)sim->d_ctrl, sim->npad, kCtrlComps,
+                       sim->N, (R*)out);
+  });
   HIP_TRY(hipGetLastError());
   return GPD_OK;
 }
@@ -1697,12 +1522,11 @@ int gpd_set_ctrl_state(gpd_sim* sim, const void* in, void* stream) {
   if (!sim->d_ctrl) return fail(GPD_EINVAL, "gpd_set_ctrl_state: the sim's action type has no controller");
   const unsigned g = grid_for(sim->N, 256);
   hipStream_t st = (hipStream_t)stream;
-  if (sim->prec == GPD_F64)
-    hipLaunchKernelGGL((rows_to_soa_kernel<double>), dim3(g), dim3(256), 0, st, (const double*)in, sim->npad, kCtrlComps,
-                       sim->N, (double*)sim->d_ctrl);
-  else
-    hipLaunchKernelGGL((rows_to_soa_kernel<float>), dim3(g), dim3(256), 0, st, (const float*)in, sim->npad, kCtrlComps,
-                       sim->N, (float*)sim->d_ctrl);
+  by_real(sim, [&](auto r) {
+    using R = decltype(r);
+    hipLaunchKernelGGL((rows_to_soa_kernel<R>), dim3(g), dim3(256), 0, st, (const R*)in, sim->npad, kCtrlComps, sim->N,
+                       (R*)sim->d_ctrl);
+  });
   HIP_TRY(hipGetLastError());
   return GPD_OK;
 }
@@ -1735,10 +1559,10 @@ void blob_header(const gpd_sim* sim, int64_t h[kBlobHeader / 8]) {
   for (size_t i = 0; i < kBlobHeader / 8; ++i) h[i] = v[i];
 }
 int sections(gpd_sim* sim, Section out[4]) {
-  out[0] = {sim->d_state, (size_t)kStateComps * sim->npad * real_size(sim)};
-  out[1] = {sim->d_ctrl, sim->d_ctrl ? (size_t)kCtrlComps * sim->npad * real_size(sim) : 0};
-  out[2] = {sim->d_ring, (size_t)sim->ring_len * sim->npad * sim->A * sizeof(float)};
-  out[3] = {sim->d_ctr, (size_t)sim->E * sizeof(int2)};
+  out[0] = {sim->d_state, state_buf_bytes(sim)};
+  out[1] = {sim->d_ctrl, sim->d_ctrl ? ctrl_buf_bytes(sim) : 0};
+  out[2] = {sim->d_ring, ring_buf_bytes(sim)};
+  out[3] = {sim->d_ctr, ctr_buf_bytes(sim)};
   return 4;
 }
 }  // namespace
@@ -1875,21 +1699,9 @@ int gpd_handoff_unpack(const uint8_t* gathered, int n_ranks, long long stride, c
   const long long nvec = rows * v.W / (vec4 ? 4 : 1) * n_ranks;
   const long long nthr = std::max(nvec, (long long)v.E * n_ranks);
   const dim3 grid(grid_for(nthr, 256)), block(256);
-  if (vec4) {
-    if (terminal_obs)
-      hipLaunchKernelGGL((handoff_unpack_kernel<4, true>), grid, block, 0, st, gathered, v, obs, reward, terminated,
-                         truncated, terminal_obs);
-    else
-      hipLaunchKernelGGL((handoff_unpack_kernel<4, false>), grid, block, 0, st, gathered, v, obs, reward, terminated,
-                         truncated, terminal_obs);
-  } else {
-    if (terminal_obs)
-      hipLaunchKernelGGL((handoff_unpack_kernel<1, true>), grid, block, 0, st, gathered, v, obs, reward, terminated,
-                         truncated, terminal_obs);
-    else
-      hipLaunchKernelGGL((handoff_unpack_kernel<1, false>), grid, block, 0, st, gathered, v, obs, reward, terminated,
-                         truncated, terminal_obs);
-  }
+  const auto k = vec4 ? (terminal_obs ? handoff_unpack_kernel<4, true> : handoff_unpack_kernel<4, false>)
+                      : (terminal_obs ? handoff_unpack_kernel<1, true> : handoff_unpack_kernel<1, false>);
+  hipLaunchKernelGGL(k, grid, block, 0, st, gathered, v, obs, reward, terminated, truncated, terminal_obs);
   HIP_TRY(hipGetLastError());
   return GPD_OK;
 }
