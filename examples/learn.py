@@ -13,6 +13,7 @@ masks as device tensors, so the whole loop (policy, env step, GAE, update) stays
     python examples/learn.py                     # HoverAviary, 4096 envs, ONE_D_RPM, Physics.PYB
     python examples/learn.py --multiagent true   # MultiHoverAviary, 2 drones
     python examples/learn.py --physics dyn       # the explicit DYN integrator instead
+    python examples/learn.py --fused-update      # the minibatch gradient as HIP kernels (policy.PpoGradKernel)
     python examples/learn.py --gpus 8 --n_envs 32768   # envs sharded over 8 GPUs, learner on rank 0
     python examples/learn.py --gpus 8 --n_envs 32768 --learner per-rank   # a learner per GPU, gradient all-reduce
 
@@ -135,6 +136,8 @@ def broadcast_params(module):
 
 def check_randomize(a):
     """--randomize needs per-env drones: Physics.DYN on one GPU.  Exits before any GPU call."""
+    if getattr(a, "fused_update", False) and a.gpus > 1 and a.learner == "per-rank":
+        raise SystemExit("learn.py: --fused-update runs one learner (--gpus 1 or --learner rank0)")
     if a.randomize is None:
         return
     if Physics(a.physics) != Physics.DYN or a.gpus != 1:
@@ -300,7 +303,7 @@ def train(multiagent=False, n_envs=4096, n_steps=64, total_timesteps=int(3e7), l
           minibatch=16384, gamma=0.99, gae_lambda=0.95, clip=0.2, vf_coef=0.5, max_grad_norm=0.5,
           eval_every=1, seed=0, device="cuda:0", act=DEFAULT_ACT, target_reward=None, max_seconds=None,
           log=print, physics=Physics.PYB, env=None, world=1, rank=0, graph=False, fused=False, randomize=None,
-          pool=256):
+          pool=256, fused_update=False):
     """PPO on the batched env.  ``env``: an already built torch-output VecEnv (e.g. the
     multi-GPU ``ShardedAviaryVecEnv``); by default one ``AviaryVecEnv`` on ``device``.
     world > 1: per-rank learners under torch.distributed — this rank trains on its own
@@ -309,8 +312,13 @@ def train(multiagent=False, n_envs=4096, n_steps=64, total_timesteps=int(3e7), l
     and the history count all ranks' samples.  ``graph``: the minibatch steps as one captured
     hipGraph (``GraphedMinibatch``; world == 1 and full minibatches only).  ``fused``: the rollout
     as ``FusedRollout`` (one policy kernel + one gpd_step per env.step, one hipGraph per rollout;
-    a single-GPU ``AviaryVecEnv``)."""
+    a single-GPU ``AviaryVecEnv``).  ``fused_update``: the minibatch gradient (gather, forward, loss,
+    backward, gradient-norm clip) as ``policy.PpoGradKernel`` - four HIP launches instead of the
+    autograd step - followed by torch's Adam (world == 1 only; it takes precedence over ``graph``)."""
     import torch.distributed as dist
+    if fused_update and world != 1:
+        raise ValueError("fused_update=True runs one learner (world == 1): the per-rank learners' gradient "
+                         "all-reduce sits between backward and clip")
     torch.manual_seed(seed)
     physics = Physics(physics)
     if env is None:
@@ -329,9 +337,13 @@ def train(multiagent=False, n_envs=4096, n_steps=64, total_timesteps=int(3e7), l
         broadcast_params(policy)
         torch.manual_seed(seed + 1000003 * rank)   # each rank samples its own actions / minibatches
         minibatch = max(1, minibatch // world)
-    graph = graph and world == 1 and torch.device(device).type == "cuda"
+    graph = graph and world == 1 and torch.device(device).type == "cuda" and not fused_update
     opt = torch.optim.Adam(policy.parameters(), lr=lr, eps=1e-5, capturable=graph)
     gstep = GraphedMinibatch(policy, opt, minibatch, n_obs, n_act, clip, vf_coef, max_grad_norm, device) if graph else None
+    gk = None
+    if fused_update:
+        from gym_pybullet_drones_routing_amd.policy import PpoGradKernel
+        gk = PpoGradKernel(policy, max_rows=minibatch)   # its views of the flat gradient are the parameters' .grad
     E = n_envs
     buf_obs = torch.zeros((n_steps, E, n_obs), device=device)
     buf_act = torch.zeros((n_steps, E, n_act), device=device)
@@ -391,6 +403,10 @@ def train(multiagent=False, n_envs=4096, n_steps=64, total_timesteps=int(3e7), l
             perm = torch.randperm(N, device=device)
             for s in range(0, N, minibatch):
                 idx = perm[s:s + minibatch]
+                if gk is not None:       # the kernel gathers the rows itself and leaves the clipped gradient
+                    gk.grad_step(idx, b_obs, b_act, b_logp, b_adv, b_ret, clip, vf_coef, max_grad_norm)
+                    opt.step()
+                    continue
                 if gstep is not None and idx.numel() == minibatch:
                     gstep.step(b_obs[idx], b_act[idx], b_logp[idx], b_adv[idx], b_ret[idx])
                     continue
@@ -455,6 +471,10 @@ def parse_args(argv=None):
                    help="replay each PPO minibatch step as one captured hipGraph (faster update; same "
                         "arithmetic up to rounding, so a different training trajectory than the default "
                         "eager loop, which reproduces the recorded runs step for step)")
+    p.add_argument("--fused-update", action="store_true",
+                   help="the minibatch gradient (row gather, forward, clipped surrogate + value loss, backward, "
+                        "gradient-norm clip) as four HIP launches (policy.PpoGradKernel), then torch's Adam; one "
+                        "learner only (--gpus 1 or --learner rank0); takes precedence over --graph")
     p.add_argument("--rollout", default="fused", choices=["fused", "eager"],
                    help="fused: one policy kernel + one env step (gpd_step, or the RCCL learner hand-off over the "
                         "ranks) per env.step, the rollout replayed as one hipGraph (FusedRollout); eager: the "
@@ -512,9 +532,10 @@ def run(a):
     fused = a.rollout == "fused" and (world == 1 or getattr(env, "graphed", False))
     policy, hist, best, target = train(multiagent=multi, n_envs=a.n_envs, total_timesteps=int(a.total_timesteps),
                                        max_seconds=a.max_seconds, physics=Physics(a.physics), device=device, env=env,
-                                       graph=a.graph, seed=a.seed, fused=fused, randomize=a.randomize, pool=a.pool)
+                                       graph=a.graph, seed=a.seed, fused=fused, randomize=a.randomize, pool=a.pool,
+                                       fused_update=a.fused_update)
     out = {"multiagent": multi, "physics": a.physics, "n_envs": a.n_envs, "gpus": world, "target_reward": target,
-           "rollout": "fused" if fused else "eager",
+           "rollout": "fused" if fused else "eager", "fused_update": bool(a.fused_update),
            "best_eval_return": best, "reached": best >= target, "history": hist}
     print(json.dumps({k: v for k, v in out.items() if k != "history"}), flush=True)
     if a.output:

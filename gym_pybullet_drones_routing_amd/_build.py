@@ -60,19 +60,21 @@ def build(force=False, verbose=False, stamps=False, variant=None, defines=()):
 
 
 POLICY_LIB = PKG_DIR / "libgpd_policy.so"
-POLICY_SOURCES = [CSRC / "gpd_policy.hip", INCLUDE / "gpd_policy.h"]
+POLICY_UNITS = [CSRC / "gpd_policy.hip", CSRC / "gpd_ppo_grad.hip"]
+POLICY_SOURCES = POLICY_UNITS + [INCLUDE / "gpd_policy.h"]
 
 
 def build_policy(force=False, verbose=False):
-    """Compile csrc/gpd_policy.hip (the fused rollout policy, include/gpd_policy.h) into
-    libgpd_policy.so for gfx950.  -ffp-contract=off: the parts written "as torch computes them"
-    (Normal sample and log-density, the time-limit bootstrap, GAE) round every operation."""
+    """Compile csrc/gpd_policy.hip (the fused rollout policy) and csrc/gpd_ppo_grad.hip (the PPO
+    minibatch gradient; both include/gpd_policy.h) into libgpd_policy.so for gfx950.
+    -ffp-contract=off: the parts written "as torch computes them" (Normal sample and log-density,
+    the time-limit bootstrap, GAE) round every operation."""
     if not force and POLICY_LIB.exists() and all(src.stat().st_mtime <= POLICY_LIB.stat().st_mtime
                                                  for src in POLICY_SOURCES):
         return POLICY_LIB
     tmp = POLICY_LIB.with_suffix(".so.tmp")
     cmd = [hipcc(), f"--offload-arch={ARCH}", "-mcode-object-version=5", "-O3", "-std=c++17", "-ffp-contract=off",
-           "-fPIC", "-shared", "-Wall", f"-I{INCLUDE}", "-o", str(tmp), str(CSRC / "gpd_policy.hip")]
+           "-fPIC", "-shared", "-Wall", f"-I{INCLUDE}", "-o", str(tmp)] + [str(u) for u in POLICY_UNITS]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + " ".join(cmd) + "\n" + res.stdout + res.stderr)

@@ -421,6 +421,11 @@ int launch_kq(const Args& A, int grid, hipStream_t st) {
 
 }  // namespace
 
+// the library's other translation unit (gpd_ppo_grad.hip) reports its errors through this one's g_err
+extern "C" __attribute__((visibility("hidden"))) int gpd_policy_fail_(int code, const char* msg) {
+  return fail(code, msg);
+}
+
 extern "C" {
 
 int gpd_policy_abi_version(void) { return GPD_POLICY_ABI_VERSION; }

@@ -23,7 +23,10 @@ GROUP_ROWS = 16                 # rows per Philox call counter (the kernel's row
 HIDDEN = 64
 MAX_OBS = 192
 MAX_ACT = 8
-EXPORTED = ("gpd_policy_rollout_step", "gpd_policy_gae", "gpd_policy_abi_version", "gpd_policy_last_error")
+EXPORTED = ("gpd_policy_rollout_step", "gpd_policy_gae", "gpd_policy_abi_version", "gpd_policy_last_error",
+            "gpd_policy_n_params", "gpd_policy_ppo_grad_workspace", "gpd_policy_ppo_grad")
+PARAM_NAMES = ("pi_w1", "pi_b1", "pi_w2", "pi_b2", "pi_w3", "pi_b3", "vf_w1", "vf_b1", "vf_w2", "vf_b2", "vf_w3",
+               "vf_b3", "log_std")
 
 
 class MlpPolicyStruct(ctypes.Structure):
@@ -56,6 +59,14 @@ def load():
                                             vp, vp, vp, vp, ctypes.c_float, vp, vp, vp]
     lib.gpd_policy_gae.restype = ci
     lib.gpd_policy_gae.argtypes = [ci, ci, vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp]
+    cf = ctypes.c_float
+    lib.gpd_policy_n_params.restype = ci
+    lib.gpd_policy_n_params.argtypes = [ci, ci]
+    lib.gpd_policy_ppo_grad_workspace.restype = ctypes.c_size_t
+    lib.gpd_policy_ppo_grad_workspace.argtypes = [ci, ci, ci, ci]
+    lib.gpd_policy_ppo_grad.restype = ci
+    lib.gpd_policy_ppo_grad.argtypes = [ctypes.POINTER(MlpPolicyStruct), ci, vp, vp, vp, vp, vp, vp, cf, cf, cf, vp, vp,
+                                        vp, ctypes.c_size_t, ci, vp]
     if lib.gpd_policy_abi_version() != GPD_POLICY_ABI_VERSION:
         raise GpdLibraryError(f"{LIB_PATH} has ABI {lib.gpd_policy_abi_version()}, expected {GPD_POLICY_ABI_VERSION}")
     _lib = lib
@@ -78,6 +89,29 @@ def _linears(seq):
     return lin
 
 
+def _module_struct(module):
+    """``module`` (``.pi``, ``.vf``, ``.log_std``) -> (gpd_mlp_policy struct over its parameters' device
+    addresses, the 13 parameters in the struct's field order, n_obs, n_act, device)."""
+    pi, vf = _linears(module.pi), _linears(module.vf)
+    if vf[2].out_features != 1:
+        raise ValueError("the critic has one output")
+    n_obs, n_act = pi[0].in_features, pi[2].out_features
+    if vf[0].in_features != n_obs:
+        raise ValueError("actor and critic read the same observation")
+    if not 1 <= n_obs <= MAX_OBS or not 1 <= n_act <= MAX_ACT:
+        raise ValueError(f"n_obs must be in [1, {MAX_OBS}] and n_act in [1, {MAX_ACT}]")
+    params = [p for lin in pi + vf for p in (lin.weight, lin.bias)] + [module.log_std]
+    dev = params[0].device
+    for p in params:
+        if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev or dev.type != "cuda":
+            raise ValueError("the fused policy reads contiguous float32 parameters on the GPU")
+    st = MlpPolicyStruct()
+    st.n_obs, st.n_act = n_obs, n_act
+    for n, p in zip(PARAM_NAMES, params):
+        setattr(st, n, p.data_ptr())
+    return st, params, n_obs, n_act, dev
+
+
 def _as_int64(x):
     """``x`` mod 2^64 as the int64 with the same bits (the device words are uint64, torch's int64)."""
     x = int(x) & 0xFFFFFFFFFFFFFFFF
@@ -95,28 +129,9 @@ class MlpPolicyKernel:
 
     def __init__(self, module, seed=0, max_rows=1 << 16):
         self._lib = load()
-        pi, vf = _linears(module.pi), _linears(module.vf)
-        if vf[2].out_features != 1:
-            raise ValueError("the critic has one output")
-        self.n_obs, self.n_act = pi[0].in_features, pi[2].out_features
-        if vf[0].in_features != self.n_obs:
-            raise ValueError("actor and critic read the same observation")
-        if not 1 <= self.n_obs <= MAX_OBS or not 1 <= self.n_act <= MAX_ACT:
-            raise ValueError(f"n_obs must be in [1, {MAX_OBS}] and n_act in [1, {MAX_ACT}]")
-        params = [p for lin in pi + vf for p in (lin.weight, lin.bias)] + [module.log_std]
-        dev = params[0].device
-        for p in params:
-            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev or dev.type != "cuda":
-                raise ValueError("the fused policy reads contiguous float32 parameters on the GPU")
-        self.device = dev
-        self._params = params            # kept alive: the struct holds their addresses
-        st = MlpPolicyStruct()
-        st.n_obs, st.n_act = self.n_obs, self.n_act
-        names = ("pi_w1", "pi_b1", "pi_w2", "pi_b2", "pi_w3", "pi_b3", "vf_w1", "vf_b1", "vf_w2", "vf_b2",
-                 "vf_w3", "vf_b3", "log_std")
-        for n, p in zip(names, params):
-            setattr(st, n, p.data_ptr())
-        self._st = st
+        # the parameters are kept alive: the struct holds their addresses
+        self._st, self._params, self.n_obs, self.n_act, self.device = _module_struct(module)
+        dev = self.device
         # {key, 0, call counter of row group 0, 1, ...} (include/gpd_policy.h)
         self.rng = torch.zeros(2 + -(-int(max_rows) // GROUP_ROWS), dtype=torch.int64, device=dev)
         self.rng[0] = _as_int64(seed)
@@ -194,3 +209,71 @@ class MlpPolicyKernel:
         _check("gpd_policy_gae", self._lib.gpd_policy_gae(
             T, E, *(ctypes.c_void_p(t.data_ptr()) for t in (rew, val, done, last_val)), float(gamma), float(lam),
             ctypes.c_void_p(adv.data_ptr()), ctypes.c_void_p(ret.data_ptr()), ctypes.c_void_p(stream)))
+
+
+class PpoGradKernel:
+    """The PPO minibatch gradient of the actor-critic ``module`` in HIP (``gpd_policy_ppo_grad``): the
+    gather of the minibatch's rows, both forward passes, the clipped surrogate + value loss of
+    examples/learn.py, the backward pass and the gradient-norm clip, with no autograd graph and no
+    optimizer: ``grad_step`` leaves the clipped gradient in ``grad`` (flat, ``PARAM_NAMES`` order),
+    whose per-parameter views are installed as each parameter's ``.grad``, so ``opt.step()`` follows.
+    Owns ``grad``, ``stats`` (policy loss, value loss, gradient norm before clipping, clip fraction)
+    and the workspace, sized for minibatches of up to ``max_rows`` rows.  ``max_blocks``: 0 = the
+    library's grid, otherwise its cap (the same inputs and max_blocks give the same bits)."""
+
+    def __init__(self, module, max_rows, max_blocks=0):
+        self._lib = load()
+        self._st, self._params, self.n_obs, self.n_act, self.device = _module_struct(module)
+        self.max_rows, self.max_blocks = int(max_rows), int(max_blocks)
+        if self.max_rows < 1 or self.max_blocks < 0:
+            raise ValueError("max_rows must be >= 1 and max_blocks >= 0")
+        self.n_params = self._lib.gpd_policy_n_params(self.n_obs, self.n_act)
+        if self.n_params != sum(p.numel() for p in self._params):
+            raise GpdLibraryError(f"{LIB_PATH} counts {self.n_params} parameters, the module has "
+                                  f"{sum(p.numel() for p in self._params)}")
+        # the workspace grows with the rows (more 16-row groups, up to the grid's cap)
+        self._ws_bytes = self._lib.gpd_policy_ppo_grad_workspace(self.n_obs, self.n_act, self.max_rows,
+                                                                 self.max_blocks)
+        if self._ws_bytes == 0:
+            raise GpdError("gpd_policy_ppo_grad_workspace", -1,
+                           self._lib.gpd_policy_last_error().decode(errors="replace"))
+        self.workspace = torch.empty(self._ws_bytes // 4, dtype=torch.float32, device=self.device)
+        self.grad = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
+        self.stats = torch.zeros(4, dtype=torch.float32, device=self.device)
+        self.views, off = [], 0
+        for p in self._params:
+            self.views.append(self.grad[off:off + p.numel()].view_as(p))
+            off += p.numel()
+        self.install()
+
+    def install(self):
+        """Make the views of ``grad`` the parameters' ``.grad`` (again, e.g. after
+        ``zero_grad(set_to_none=True)``)."""
+        for p, v in zip(self._params, self.views):
+            p.grad = v
+
+    def _buf(self, t, name, dtype=torch.float32):
+        if not (t.is_cuda and t.device == self.device and t.dtype == dtype and t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor on {self.device}")
+        return ctypes.c_void_p(t.data_ptr())
+
+    def grad_step(self, idx, obs, act, logp, adv, ret, clip, vf_coef, max_grad_norm, n_rows=None):
+        """One minibatch: rows ``idx`` (int64 device tensor, or None for rows 0 .. n_rows - 1) of the
+        flattened rollout buffers ``obs [N, n_obs]``, ``act [N, n_act]``, ``logp``, ``adv``, ``ret [N]``.
+        Asynchronous on the current stream and capturable.  The indices are not checked on the host
+        (that would read them back): the caller keeps them inside the buffers."""
+        N = logp.numel()
+        if obs.numel() != N * self.n_obs or act.numel() != N * self.n_act or adv.numel() != N or ret.numel() != N:
+            raise ValueError(f"the buffers must hold the same {N} rows: obs {tuple(obs.shape)}, act {tuple(act.shape)}, "
+                             f"adv {tuple(adv.shape)}, ret {tuple(ret.shape)}")
+        n = int(idx.numel()) if idx is not None else int(N if n_rows is None else n_rows)
+        if not 1 <= n <= self.max_rows or (idx is None and n > N):
+            raise ValueError(f"a minibatch of {n} rows: this kernel was built for 1 .. {self.max_rows} rows "
+                             f"of buffers that hold them")
+        ip = self._buf(idx, "idx", torch.int64) if idx is not None else None
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _check("gpd_policy_ppo_grad", self._lib.gpd_policy_ppo_grad(
+            ctypes.byref(self._st), n, ip, self._buf(obs, "obs"), self._buf(act, "act"), self._buf(logp, "logp"),
+            self._buf(adv, "adv"), self._buf(ret, "ret"), float(clip), float(vf_coef), float(max_grad_norm),
+            ctypes.c_void_p(self.grad.data_ptr()), ctypes.c_void_p(self.stats.data_ptr()),
+            ctypes.c_void_p(self.workspace.data_ptr()), self._ws_bytes, self.max_blocks, ctypes.c_void_p(stream)))

@@ -71,6 +71,32 @@ int gpd_policy_rollout_step(const gpd_mlp_policy* policy, int n_rows, const floa
 int gpd_policy_gae(int n_steps, int n_rows, const float* rew, const float* val, const float* done,
                    const float* last_val, double gamma, double lam, float* adv, float* ret, void* stream);
 
+/* The PPO minibatch gradient (csrc/gpd_ppo_grad.hip): loss, backward and gradient-norm clip of
+ * examples/learn.py's minibatch step, up to the optimizer.
+ *   mu = pi(obs), scale = exp(log_std)
+ *   logp  = sum_a [-(act - mu)^2 / (2 scale^2) - log_std - log sqrt(2 pi)]
+ *   ratio = exp(logp - old_logp),  A = (adv - mean) / (std + 1e-8)   (mean, unbiased std over the minibatch)
+ *   loss  = -mean(min(ratio A, clamp(ratio, 1 - clip, 1 + clip) A)) + vf_coef mean((vf(obs) - ret)^2)
+ * obs [.][n_obs], act [.][n_act] (the buffered, unclipped sample), old_logp, adv, ret [.]: the flattened
+ * rollout buffers; idx [n_rows] (int64, nullable) selects the minibatch's rows, gathered by the kernel
+ * (NULL: rows 0 .. n_rows - 1; the caller keeps every index inside the buffers).
+ *   grad  [gpd_policy_n_params]  d loss / d parameters, flat, in gpd_mlp_policy's field order
+ *         (pi_w1, pi_b1, ..., vf_b3, log_std), scaled by min(1, max_grad_norm / (norm + 1e-6)) as
+ *         torch clip_grad_norm_ does when max_grad_norm > 0
+ *   stats [4]  policy loss, value loss, gradient norm before clipping, clip fraction
+ *   workspace  >= gpd_policy_ppo_grad_workspace(n_obs, n_act, n_rows, max_blocks) bytes, 16-B aligned,
+ *         contents irrelevant on entry
+ *   max_blocks 0 = the library's choice; otherwise the cap of the main kernel's grid (a block then
+ *         loops over several 16-row groups)
+ * Four launches on `stream`, no host state, no atomics: the same inputs and max_blocks give the same
+ * bits.  Every check runs before any device call (GPD_EINVAL, -1). */
+int gpd_policy_n_params(int n_obs, int n_act);                 /* -1: n_obs / n_act out of range */
+size_t gpd_policy_ppo_grad_workspace(int n_obs, int n_act, int n_rows, int max_blocks);   /* 0: invalid */
+int gpd_policy_ppo_grad(const gpd_mlp_policy* policy, int n_rows, const int64_t* idx, const float* obs,
+                        const float* act, const float* old_logp, const float* adv, const float* ret,
+                        float clip_range, float vf_coef, float max_grad_norm, float* grad, float* stats,
+                        void* workspace, size_t workspace_bytes, int max_blocks, void* stream);
+
 int gpd_policy_abi_version(void);
 const char* gpd_policy_last_error(void);
 

@@ -1,0 +1,101 @@
+"""gpd_policy_ppo_grad's host side (no GPU): the argument checks that run before any device call,
+the parameter count, the workspace size, and examples/learn.py's --fused-update plumbing."""
+import ctypes
+import os
+import re
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "examples"))
+
+
+@pytest.fixture(scope="module")
+def pl():
+    from gym_pybullet_drones_routing_amd import _build, policy
+    _build.build_policy()
+    return policy.load()
+
+
+def test_header_binding_and_library_agree(pl):
+    from gym_pybullet_drones_routing_amd import policy
+    text = open(os.path.join(ROOT, "include", "gpd_policy.h")).read()
+    declared = set(re.findall(r"\b(gpd_policy_[a-z0-9_]+)\s*\(", text))
+    assert declared == set(policy.EXPORTED)
+    assert {"gpd_policy_n_params", "gpd_policy_ppo_grad_workspace", "gpd_policy_ppo_grad"} <= declared
+    out = os.popen(f"nm -D --defined-only {pl._name}").read()
+    for name in declared:
+        assert re.search(rf"\bT {name}\b", out), f"{name} not exported as a text symbol"
+    assert "gpd_policy_fail_" not in out            # the translation units' shared error hook stays internal
+    assert pl.gpd_policy_abi_version() == 2          # additive: the ABI version did not move
+
+
+def test_n_params_and_workspace(pl):
+    import learn
+    for n_obs, n_act in ((72, 4), (27, 1), (192, 8)):
+        want = sum(p.numel() for p in learn.ActorCritic(n_obs, n_act).parameters())
+        assert pl.gpd_policy_n_params(n_obs, n_act) == want
+    assert pl.gpd_policy_n_params(193, 4) == -1 and b"n_obs" in pl.gpd_policy_last_error()
+    assert pl.gpd_policy_n_params(72, 9) == -1
+    ws = [pl.gpd_policy_ppo_grad_workspace(72, 4, 16384, b) for b in (1, 2, 64, 256)]
+    assert all(a < b for a, b in zip(ws, ws[1:]))                      # one slab per block
+    n = pl.gpd_policy_n_params(72, 4)
+    assert ws[1] - ws[0] >= 4 * n and (ws[1] - ws[0]) % 16 == 0
+    # the grid never exceeds the row groups: 37 rows are 3 groups, whatever the cap
+    assert pl.gpd_policy_ppo_grad_workspace(72, 4, 37, 0) == pl.gpd_policy_ppo_grad_workspace(72, 4, 37, 3) \
+        == pl.gpd_policy_ppo_grad_workspace(72, 4, 37, 200)
+    assert pl.gpd_policy_ppo_grad_workspace(72, 4, 0, 0) == 0
+    assert pl.gpd_policy_ppo_grad_workspace(72, 4, 16, -1) == 0
+
+
+def test_refusals_before_any_device_call(pl):
+    from gym_pybullet_drones_routing_amd import policy
+    st = policy.MlpPolicyStruct()
+    st.n_obs, st.n_act = 72, 4
+    fake = 256          # never dereferenced: every call below fails its host-side checks
+    for n in policy.PARAM_NAMES:
+        setattr(st, n, fake)
+    vp = ctypes.c_void_p
+    need = pl.gpd_policy_ppo_grad_workspace(72, 4, 100, 0)
+
+    def call(policy_=st, n_rows=100, idx=None, bufs=(fake,) * 5, grad=fake, stats=fake, ws=fake, ws_bytes=need,
+             max_blocks=0):
+        return pl.gpd_policy_ppo_grad(ctypes.byref(policy_) if policy_ is not None else None, n_rows,
+                                      vp(idx) if idx else None, *(vp(b) if b else None for b in bufs), 0.2, 0.5, 0.5,
+                                      vp(grad) if grad else None, vp(stats) if stats else None,
+                                      vp(ws) if ws else None, ws_bytes, max_blocks, None)
+
+    def refused(msg, **kw):
+        assert call(**kw) == -1
+        assert msg in pl.gpd_policy_last_error(), pl.gpd_policy_last_error()
+
+    refused(b"NULL policy", policy_=None)
+    refused(b"n_rows < 1", n_rows=0)
+    refused(b"NULL rollout buffer", bufs=(fake, None, fake, fake, fake))
+    refused(b"NULL grad, stats or workspace", grad=None)
+    refused(b"NULL grad, stats or workspace", ws=None)
+    refused(b"max_blocks", max_blocks=-1)
+    refused(b"workspace holds", ws_bytes=need - 1)
+    refused(b"misaligned", ws=fake + 8)
+    refused(b"misaligned", idx=fake + 4)
+    refused(b"misaligned", bufs=(fake + 2, fake, fake, fake, fake))
+    wide = policy.MlpPolicyStruct()
+    ctypes.memmove(ctypes.byref(wide), ctypes.byref(st), ctypes.sizeof(st))
+    wide.n_obs = policy.MAX_OBS + 1
+    refused(b"n_obs must be in [1, 192]", policy_=wide)
+    wide.n_obs, wide.n_act = 72, policy.MAX_ACT + 1
+    refused(b"n_act must be in [1, 8]", policy_=wide)
+    wide.n_act, wide.vf_w2 = 4, None
+    refused(b"NULL weight", policy_=wide)
+
+
+def test_learn_fused_update_plumbing():
+    import learn
+    assert learn.parse_args([]).fused_update is False
+    assert learn.parse_args(["--fused-update"]).fused_update is True
+    # refused before the device (or an env) is touched: this runs on a machine without a GPU
+    with pytest.raises(ValueError, match="world == 1"):
+        learn.train(fused_update=True, world=2)
+    with pytest.raises(SystemExit, match="--fused-update"):
+        learn.check_randomize(learn.parse_args(["--fused-update", "--gpus", "2", "--learner", "per-rank"]))
