@@ -11,7 +11,8 @@ PKG_DIR = pathlib.Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 INCLUDE = PKG_DIR.parent / "include"
 LIB_PATH = PKG_DIR / "libgpd.so"
-# every header and source under csrc/: a header added later cannot be missed by needs_build()
+# every header and source directly under csrc/ (the globs are not recursive: csrc/policy/ is
+# libgpd_policy.so's): a header added later cannot be missed by needs_build()
 SOURCES = sorted(CSRC.glob("*.h")) + sorted(CSRC.glob("*.hip")) + [INCLUDE / "gpd.h"]
 ARCH = os.environ.get("GPD_OFFLOAD_ARCH", "gfx950")
 # kernarg preloading: the step kernel's leading scalar arguments arrive in SGPRs.
@@ -60,21 +61,25 @@ def build(force=False, verbose=False, stamps=False, variant=None, defines=()):
 
 
 POLICY_LIB = PKG_DIR / "libgpd_policy.so"
-POLICY_UNITS = [CSRC / "gpd_policy.hip", CSRC / "gpd_ppo_grad.hip"]
-POLICY_SOURCES = POLICY_UNITS + [INCLUDE / "gpd_policy.h"]
+POLICY_DIR = CSRC / "policy"
+POLICY_UNITS = sorted(POLICY_DIR.glob("*.hip"))
+POLICY_SOURCES = sorted(POLICY_DIR.glob("*.h")) + POLICY_UNITS + [INCLUDE / "gpd_policy.h"]
+# -ffp-contract=off: the parts written "as torch computes them" (Normal sample and log-density, the
+# time-limit bootstrap, GAE) round every operation.  (scripts/kernel_diff.py --policy compiles the
+# device assembly with the same list)
+POLICY_FLAGS = [f"--offload-arch={ARCH}", "-mcode-object-version=5", "-O3", "-std=c++17", "-ffp-contract=off"]
 
 
 def build_policy(force=False, verbose=False):
-    """Compile csrc/gpd_policy.hip (the fused rollout policy) and csrc/gpd_ppo_grad.hip (the PPO
-    minibatch gradient; both include/gpd_policy.h) into libgpd_policy.so for gfx950.
-    -ffp-contract=off: the parts written "as torch computes them" (Normal sample and log-density,
-    the time-limit bootstrap, GAE) round every operation."""
+    """Compile the units of csrc/policy/ (gpd_policy.hip: the fused rollout policy; gpd_ppo_grad.hip: the
+    PPO minibatch gradient; both include/gpd_policy.h, their shared code in gpd_policy_mlp.h) into
+    libgpd_policy.so for gfx950."""
     if not force and POLICY_LIB.exists() and all(src.stat().st_mtime <= POLICY_LIB.stat().st_mtime
                                                  for src in POLICY_SOURCES):
         return POLICY_LIB
     tmp = POLICY_LIB.with_suffix(".so.tmp")
-    cmd = [hipcc(), f"--offload-arch={ARCH}", "-mcode-object-version=5", "-O3", "-std=c++17", "-ffp-contract=off",
-           "-fPIC", "-shared", "-Wall", f"-I{INCLUDE}", "-o", str(tmp)] + [str(u) for u in POLICY_UNITS]
+    cmd = [hipcc()] + POLICY_FLAGS + ["-fPIC", "-shared", "-Wall", f"-I{INCLUDE}", "-o", str(tmp)] + [
+        str(u) for u in POLICY_UNITS]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + " ".join(cmd) + "\n" + res.stdout + res.stderr)

@@ -31,40 +31,22 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdint>
-#include <string>
 
-#include "../../include/gpd_policy.h"
+#include "gpd_policy.h"
+#include "gpd_policy_mlp.h"
+
+using namespace gpd_policy;
 
 namespace {
-
 thread_local std::string g_err;
+}
 
-int fail(int code, const std::string& msg) {
+int gpd_policy::fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
 
-constexpr int kOk = 0, kEinval = -1, kEhip = -2, kEunsupported = -4;   // gpd.h GPD_OK / GPD_E*
-
-#define HIP_TRY(expr)                                                                  \
-  do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
-    if (e_ != hipSuccess) return fail(kEhip, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-constexpr int H = GPD_POLICY_HIDDEN;
-constexpr int kWaves = 4;                      // waves per block: neurons 16w .. 16w+15 each
-constexpr int kBlock = kWaves * 64;
-constexpr int kM = 16;                         // rows per group (MFMA M)
-constexpr int kXs = kM + 1;                    // LDS row stride of the k-major tiles (odd: no bank conflicts)
-constexpr int kRes = 16;                       // LDS stride of a row's outputs (n_act + 1 <= 9)
-constexpr int kMaxKq = GPD_POLICY_MAX_OBS / 4;
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-struct Net {
-  const float *w1, *b1, *w2, *b2, *w3, *b3;
-};
+namespace {
 
 struct Args {
   Net pi, vf;
@@ -105,66 +87,30 @@ __device__ inline float std_normal(uint64_t seed, uint64_t call, int row, int a)
   return (a & 1) ? rad * s : rad * co;
 }
 
-template <int CTRL>
-__device__ inline float dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-// the sum over the 16 lanes of a DPP row (lanes 16r .. 16r+15), in every lane of the row
-__device__ inline float row16_sum(float v) {
-  v += dpp<0x140>(v);   // row_mirror: i <-> 15 - i
-  v += dpp<0x141>(v);   // row_half_mirror: i <-> 7 - i within each half
-  v += dpp<0x4E>(v);    // quad_perm [2, 3, 0, 1]
-  v += dpp<0xB1>(v);    // quad_perm [1, 0, 3, 2]
-  return v;
-}
-
 struct Lds {
   float xt[kMaxKq * 4 * kXs];      // the group's input rows, k-major: xt[k * kXs + row]
   float xb[kMaxKq * 4 * kXs];      // its terminal rows (bootstrap), the same layout
   float h1v[H * kXs], h1p[H * kXs], h1b[H * kXs];   // layer-1 activations, neuron-major
-  float part[kWaves][kM][kRes];    // per wave: its 16 neurons' share of the output sums
+  Part part;                       // per wave: its 16 neurons' share of the output sums
   float res[kM][kRes];             // per row: mu[0..n_act), value at n_act, V(terminal row) at n_act + 1
   float lp[kM][GPD_POLICY_MAX_ACT];
   float b3[GPD_POLICY_MAX_ACT + 1];   // output biases: mu_0 .. mu_{n_act-1}, value
 };
 
-// This lane's slice of the weights: B operands W1[j][g KQ + s] (s < KQ), W2[j][16 g + s], output
-// weights W3[o][j], biases of neuron j (j = 16 w + (l & 15), g = l >> 4).  The K index of MFMA
-// step s and operand slot g is g KQ + s (not 4 s + g): a lane's weights of one layer are then
-// contiguous in the row-major nn.Linear weight, so they arrive as float4 loads (a quarter of the
-// load instructions; one scalar load per element took ~2 us of address processing per launch).
+// This lane's slice of the weights: the B operands of both layers (W[j][k_of(g, s)]), the output weights W3[o][j],
+// the biases of neuron j (j = 16 w + (l & 15), g = l >> 4).
 template <int NA, int KQ>
 struct Regs {
   float w1v[KQ], w1p[KQ], w2v[16], w2p[16], w3p[NA], w3v, b1v, b1p, b2v, b2p;
   float sc;           // exp(log_std[a]) of this lane's action a = threadIdx.x % NA (sampling lanes)
 };
 
-template <int N>
-__device__ inline void load_slice(float (&dst)[N], const float* __restrict__ row, int k0, int n, bool on) {
-  // dst[s] = row[k0 + s] (0 past n or when !on); float4 / float2 loads when the slice is 16- / 8-B aligned
-  if (N % 4 == 0 && on && (n & 3) == 0 && (k0 & 3) == 0 && ((uintptr_t)row & 15) == 0 && k0 + N <= n) {
-#pragma unroll
-    for (int q = 0; q < N / 4; ++q) {
-      const float4 v = reinterpret_cast<const float4*>(row + k0)[q];
-      dst[4 * q] = v.x; dst[4 * q + 1] = v.y; dst[4 * q + 2] = v.z; dst[4 * q + 3] = v.w;
-    }
-  } else if (N % 2 == 0 && on && (n & 1) == 0 && (k0 & 1) == 0 && ((uintptr_t)row & 7) == 0 && k0 + N <= n) {
-#pragma unroll
-    for (int q = 0; q < N / 2; ++q) {   // float2 (KQ = 18: the slices start 72 B apart)
-      const float2 v = reinterpret_cast<const float2*>(row + k0)[q];
-      dst[2 * q] = v.x; dst[2 * q + 1] = v.y;
-    }
-  } else {
-#pragma unroll
-    for (int s = 0; s < N; ++s) dst[s] = on && k0 + s < n ? row[k0 + s] : 0.0f;
-  }
-}
 template <int NA, int KQ>
 __device__ inline void load_regs(const Args& A, Regs<NA, KQ>& R, int j, int g) {
-  load_slice<KQ>(R.w1v, A.vf.w1 + (size_t)j * A.n_obs, g * KQ, A.n_obs, true);
-  load_slice<KQ>(R.w1p, A.actor ? A.pi.w1 + (size_t)j * A.n_obs : A.vf.w1, g * KQ, A.n_obs, A.actor);
-  load_slice<16>(R.w2v, A.vf.w2 + (size_t)j * H, 16 * g, H, true);
-  load_slice<16>(R.w2p, A.actor ? A.pi.w2 + (size_t)j * H : A.vf.w2, 16 * g, H, A.actor);
+  load_slice<KQ>(R.w1v, A.vf.w1 + (size_t)j * A.n_obs, k_of<KQ>(g, 0), A.n_obs);
+  load_slice<KQ>(R.w1p, A.actor ? A.pi.w1 + (size_t)j * A.n_obs : A.vf.w1, k_of<KQ>(g, 0), A.n_obs, A.actor);
+  load_slice<16>(R.w2v, A.vf.w2 + (size_t)j * H, k_of<16>(g, 0), H);
+  load_slice<16>(R.w2p, A.actor ? A.pi.w2 + (size_t)j * H : A.vf.w2, k_of<16>(g, 0), H, A.actor);
 #pragma unroll
   for (int a = 0; a < NA; ++a) R.w3p[a] = A.actor ? A.pi.w3[a * H + j] : 0.0f;
   R.w3v = A.vf.w3[j];
@@ -220,7 +166,7 @@ __device__ inline void forward(Lds& L, const Args& A, const Regs<NA, KQ>& R, int
   f4 av = {0.f, 0.f, 0.f, 0.f}, ap = {0.f, 0.f, 0.f, 0.f}, ab = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int s = 0; s < KQ; ++s) {
-    const int o = (g * KQ + s) * kXs + i;              // A[row i][k = g KQ + s]
+    const int o = a_off<KQ>(g, s, i);
     if (CRIT || ACT) {
       const float x = L.xt[o];
       if (CRIT) av = __builtin_amdgcn_mfma_f32_16x16x4f32(x, R.w1v[s], av, 0, 0, 0);
@@ -241,7 +187,7 @@ __device__ inline void forward(Lds& L, const Args& A, const Regs<NA, KQ>& R, int
   ab = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int s = 0; s < 16; ++s) {
-    const int o = (16 * g + s) * kXs + i;
+    const int o = a_off<16>(g, s, i);
     if (CRIT) av = __builtin_amdgcn_mfma_f32_16x16x4f32(L.h1v[o], R.w2v[s], av, 0, 0, 0);
     if (ACT) ap = __builtin_amdgcn_mfma_f32_16x16x4f32(L.h1p[o], R.w2p[s], ap, 0, 0, 0);
     if (BOOT) ab = __builtin_amdgcn_mfma_f32_16x16x4f32(L.h1b[o], R.w2v[s], ab, 0, 0, 0);
@@ -250,12 +196,12 @@ __device__ inline void forward(Lds& L, const Args& A, const Regs<NA, KQ>& R, int
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     float sv = 0.0f, sb = 0.0f, sp[NA];
-    if (CRIT) sv = row16_sum(R.w3v * tanhf(av[r] + R.b2v));
-    if (BOOT) sb = row16_sum(R.w3v * tanhf(ab[r] + R.b2v));
+    if (CRIT) sv = out_share(R.w3v, tanhf(av[r] + R.b2v));
+    if (BOOT) sb = out_share(R.w3v, tanhf(ab[r] + R.b2v));
     if (ACT) {
       const float hp = tanhf(ap[r] + R.b2p);
 #pragma unroll
-      for (int a = 0; a < NA; ++a) sp[a] = row16_sum(R.w3p[a] * hp);
+      for (int a = 0; a < NA; ++a) sp[a] = out_share(R.w3p[a], hp);
     }
     if (i == 0) {
       if (CRIT) L.part[w][4 * g + r][NA] = sv;
@@ -271,12 +217,9 @@ __device__ inline void forward(Lds& L, const Args& A, const Regs<NA, KQ>& R, int
   const int t = threadIdx.x;
   if (t < kM * (NA + 2)) {
     const int row = t / (NA + 2), o = t - row * (NA + 2);
-    if ((ACT && o < NA) || (CRIT && o == NA) || (BOOT && o == NA + 1)) {
-      float acc = L.part[0][row][o];
-#pragma unroll
-      for (int ww = 1; ww < kWaves; ++ww) acc += L.part[ww][row][o];
-      L.res[row][o] = acc + L.b3[o < NA + 1 ? o : NA];   // (an index into R, even a select chain, puts R in scratch)
-    }
+    // (the biases come from LDS: an index into R, even a select chain, puts R in scratch)
+    if ((ACT && o < NA) || (CRIT && o == NA) || (BOOT && o == NA + 1))
+      L.res[row][o] = out_sum(L.part, row, o) + L.b3[o < NA + 1 ? o : NA];
   }
   __syncthreads();
 }
@@ -401,30 +344,16 @@ __global__ void __launch_bounds__(256) gae_kernel(int T, int n, const float* __r
   }
 }
 
-template <int NA, int KQ>
-int launch(const Args& A, int grid, hipStream_t st) {
-  hipLaunchKernelGGL((rollout_kernel<NA, KQ>), dim3(grid), dim3(kBlock), 0, st, A);
-  HIP_TRY(hipGetLastError());
-  return kOk;
-}
-// the weight slices live in VGPRs: the layer-1 slice sized by the obs width's bucket (18 / 36:
-// the KIN observation of one / two RPM drones, 72 / 144 wide, without padding MFMA steps)
 template <int NA>
-int launch_kq(const Args& A, int grid, hipStream_t st) {
-  if (A.kq <= 8) return launch<NA, 8>(A, grid, st);
-  if (A.kq <= 16) return launch<NA, 16>(A, grid, st);
-  if (A.kq <= 18) return launch<NA, 18>(A, grid, st);
-  if (A.kq <= 24) return launch<NA, 24>(A, grid, st);
-  if (A.kq <= 36) return launch<NA, 36>(A, grid, st);
-  return launch<NA, kMaxKq>(A, grid, st);
+int launch(const Args& A, int grid, hipStream_t st) {
+  return with_kq(A.kq, [&](auto kq) {
+    hipLaunchKernelGGL((rollout_kernel<NA, decltype(kq)::value>), dim3(grid), dim3(kBlock), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    return kOk;
+  });
 }
 
 }  // namespace
-
-// the library's other translation unit (gpd_ppo_grad.hip) reports its errors through this one's g_err
-extern "C" __attribute__((visibility("hidden"))) int gpd_policy_fail_(int code, const char* msg) {
-  return fail(code, msg);
-}
 
 extern "C" {
 
@@ -445,8 +374,7 @@ int gpd_policy_rollout_step(const gpd_mlp_policy* p, int n_rows, const float* ob
   if (!p->vf_w1 || !p->vf_b1 || !p->vf_w2 || !p->vf_b2 || !p->vf_w3 || !p->vf_b3)
     return fail(kEinval, "gpd_policy_rollout_step: NULL critic weight");
   Args A = {};
-  A.pi = {p->pi_w1, p->pi_b1, p->pi_w2, p->pi_b2, p->pi_w3, p->pi_b3};
-  A.vf = {p->vf_w1, p->vf_b1, p->vf_w2, p->vf_b2, p->vf_w3, p->vf_b3};
+  nets_of(p, A.pi, A.vf);
   A.log_std = p->log_std;
   A.n_obs = p->n_obs;
   A.kq = (p->n_obs + 3) / 4;
@@ -475,14 +403,14 @@ int gpd_policy_rollout_step(const gpd_mlp_policy* p, int n_rows, const float* ob
   const int grid = groups < 2048 ? groups : 2048;
   hipStream_t st = (hipStream_t)stream;
   switch (p->n_act) {
-    case 1: return launch_kq<1>(A, grid, st);
-    case 2: return launch_kq<2>(A, grid, st);
-    case 3: return launch_kq<3>(A, grid, st);
-    case 4: return launch_kq<4>(A, grid, st);
-    case 5: return launch_kq<5>(A, grid, st);
-    case 6: return launch_kq<6>(A, grid, st);
-    case 7: return launch_kq<7>(A, grid, st);
-    default: return launch_kq<8>(A, grid, st);
+    case 1: return launch<1>(A, grid, st);
+    case 2: return launch<2>(A, grid, st);
+    case 3: return launch<3>(A, grid, st);
+    case 4: return launch<4>(A, grid, st);
+    case 5: return launch<5>(A, grid, st);
+    case 6: return launch<6>(A, grid, st);
+    case 7: return launch<7>(A, grid, st);
+    default: return launch<8>(A, grid, st);
   }
 }
 

@@ -5,7 +5,8 @@
 // Everything up to the clipped gradient is four launches here (Adam stays torch's):
 //   1. adv_stats_kernel   mean and unbiased std of adv[idx]            (one block, fixed order)
 //   2. grad_kernel        blocks of four waves over 16-row groups: the gather, the forward pass as
-//                         gpd_policy.hip's forward<> computes it (same K order, same output sums),
+//                         gpd_policy.hip's forward<> computes it (K order and output sums from
+//                         gpd_policy_mlp.h: the same bits for mu and V),
 //                         the per-row dL/dmu, dL/dlog_std, dL/dv, and the backward pass of both MLPs
 //                         on v_mfma_f32_16x16x4_f32; a block keeps its weight gradients in registers
 //                         over all of its groups and stores them once, as one slab of the workspace
@@ -32,29 +33,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdint>
-#include <string>
 
-#include "../../include/gpd_policy.h"
+#include "gpd_policy.h"
+#include "gpd_policy_mlp.h"
 
-// gpd_policy.hip: sets gpd_policy_last_error() and returns `code` (hidden: not exported)
-extern "C" __attribute__((visibility("hidden"))) int gpd_policy_fail_(int code, const char* msg);
+using namespace gpd_policy;
 
 namespace {
 
-constexpr int kOk = 0, kEinval = -1, kEhip = -2;
-
-#define HIP_TRY(expr)                                                                            \
-  do {                                                                                           \
-    hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess)                                                                        \
-      return gpd_policy_fail_(kEhip, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
-
-constexpr int H = GPD_POLICY_HIDDEN;
-constexpr int kBlock = 256;                    // four waves: neurons 16w .. 16w+15 each
-constexpr int kM = 16;                         // rows per group (MFMA M)
-constexpr int kXs = kM + 1;                    // LDS row stride of the k-major tiles
 constexpr int kMaxAct = GPD_POLICY_MAX_ACT;
 constexpr int kV = kMaxAct;                    // column of the value / dL/dv beside the actions' 0 .. 7
 constexpr int kRv = 33;                        // row stride of Lds::rowv
@@ -63,11 +49,6 @@ constexpr int kDefaultBlocks = 256;            // one block per CU
 constexpr int kHead = 16;                      // workspace floats: adv mean, std + 1e-8, ...
 constexpr int kNormParts = 256;                // ... then reduce_kernel's partial squared norms, then the slabs
 constexpr int kStatsThreads = 1024, kStatsBatch = 8;
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-struct Net {
-  const float *w1, *b1, *w2, *b2, *w3, *b3;
-};
 
 struct Args {
   Net pi, vf;
@@ -105,45 +86,11 @@ __host__ __device__ inline Offsets offsets(int n_obs, int n_act) {
   return o;
 }
 
-template <int CTRL>
-__device__ inline float dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-// the sum over the 16 lanes of a DPP row (lanes 16r .. 16r+15), in every lane of the row
-__device__ inline float row16_sum(float v) {
-  v += dpp<0x140>(v);   // row_mirror
-  v += dpp<0x141>(v);   // row_half_mirror
-  v += dpp<0x4E>(v);    // quad_perm [2, 3, 0, 1]
-  v += dpp<0xB1>(v);    // quad_perm [1, 0, 3, 2]
-  return v;
-}
-
-// dst[s] = row[k0 + s] (0 past n); float4 / float2 loads when the slice is 16- / 8-B aligned
-template <int N>
-__device__ inline void load_slice(float (&dst)[N], const float* __restrict__ row, int k0, int n) {
-  if (N % 4 == 0 && (n & 3) == 0 && (k0 & 3) == 0 && ((uintptr_t)row & 15) == 0 && k0 + N <= n) {
-#pragma unroll
-    for (int q = 0; q < N / 4; ++q) {
-      const float4 v = reinterpret_cast<const float4*>(row + k0)[q];
-      dst[4 * q] = v.x; dst[4 * q + 1] = v.y; dst[4 * q + 2] = v.z; dst[4 * q + 3] = v.w;
-    }
-  } else if (N % 2 == 0 && (n & 1) == 0 && (k0 & 1) == 0 && ((uintptr_t)row & 7) == 0 && k0 + N <= n) {
-#pragma unroll
-    for (int q = 0; q < N / 2; ++q) {
-      const float2 v = reinterpret_cast<const float2*>(row + k0)[q];
-      dst[2 * q] = v.x; dst[2 * q + 1] = v.y;
-    }
-  } else {
-#pragma unroll
-    for (int s = 0; s < N; ++s) dst[s] = k0 + s < n ? row[k0 + s] : 0.0f;
-  }
-}
-
 struct Lds {
   float xt[kMaxKc * 16 * kXs];          // the group's input rows, k-major: xt[k * kXs + row], 0 past n_obs
   float h1v[H * kXs], h1p[H * kXs];     // layer-1 activations, neuron-major
   float dzv[H * kXs], dzp[H * kXs];     // dL/dz2, neuron-major
-  float part[4][kM][16];                // per wave: its 16 neurons' share of the output sums
+  Part part;                            // per wave: its 16 neurons' share of the output sums
   float rowv[kM][kRv];                  // per row: dL/dmu 0..7, dL/dv 8, (9..15 zero), dL/dlog_std 16..23,
                                         // policy loss 24, value loss 25, clipped 26
   float red[4][4][H];                   // the bias gradients' partial sums per lane group
@@ -160,10 +107,10 @@ struct NetRegs {
 
 template <int KQ>
 __device__ inline void load_net(NetRegs<KQ>& R, const Net& N, int n_obs, int j, int g, int col) {
-  load_slice<KQ>(R.w1, N.w1 + (size_t)j * n_obs, g * KQ, n_obs);
-  load_slice<16>(R.w2, N.w2 + (size_t)j * H, 16 * g, H);
+  load_slice<KQ>(R.w1, N.w1 + (size_t)j * n_obs, k_of<KQ>(g, 0), n_obs);
+  load_slice<16>(R.w2, N.w2 + (size_t)j * H, k_of<16>(g, 0), H);
 #pragma unroll
-  for (int s = 0; s < 16; ++s) R.w2t[s] = N.w2[(16 * g + s) * H + col];
+  for (int s = 0; s < 16; ++s) R.w2t[s] = N.w2[k_of<16>(g, s) * H + col];
   R.b1 = N.b1[j]; R.b2 = N.b2[j];
   const f4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -220,7 +167,7 @@ __device__ inline void backward(Lds& L, NetRegs<KQ>& R, const float* h1l, float*
   f4 dh1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int s = 0; s < 16; ++s)
-    dh1 = __builtin_amdgcn_mfma_f32_16x16x4f32(dzl[(16 * g + s) * kXs + i], R.w2t[s], dh1, 0, 0, 0);
+    dh1 = __builtin_amdgcn_mfma_f32_16x16x4f32(dzl[k_of<16>(g, s) * kXs + i], R.w2t[s], dh1, 0, 0, 0);
   f4 dz1;
 #pragma unroll
   for (int r = 0; r < 4; ++r) dz1[r] = dh1[r] * (1.0f - h1[r] * h1[r]);
@@ -283,11 +230,11 @@ __global__ void __launch_bounds__(kBlock) gpd_ppo_grad_kernel(Args A) {
     __syncthreads();
     if (row0 + stride < A.n_rows) load_group(G, A, src_next, row0 + stride + ri, c);
     src_next = source_row(A, row0 + 2 * stride + ri);
-    // ---- forward, as gpd_policy.hip's forward<>: K index of step s, slot g is g KQ + s
+    // ---- forward, as gpd_policy.hip's forward<>: the K order, tile offsets and output sums are gpd_policy_mlp.h's
     f4 av = {0.f, 0.f, 0.f, 0.f}, ap = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < KQ; ++s) {
-      const float x = L.xt[(g * KQ + s) * kXs + i];
+      const float x = L.xt[a_off<KQ>(g, s, i)];
       av = __builtin_amdgcn_mfma_f32_16x16x4f32(x, V.w1[s], av, 0, 0, 0);
       ap = __builtin_amdgcn_mfma_f32_16x16x4f32(x, P.w1[s], ap, 0, 0, 0);
     }
@@ -304,7 +251,7 @@ __global__ void __launch_bounds__(kBlock) gpd_ppo_grad_kernel(Args A) {
     ap = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
-      const int o = (16 * g + s) * kXs + i;
+      const int o = a_off<16>(g, s, i);
       av = __builtin_amdgcn_mfma_f32_16x16x4f32(L.h1v[o], V.w2[s], av, 0, 0, 0);
       ap = __builtin_amdgcn_mfma_f32_16x16x4f32(L.h1p[o], P.w2[s], ap, 0, 0, 0);
     }
@@ -313,12 +260,12 @@ __global__ void __launch_bounds__(kBlock) gpd_ppo_grad_kernel(Args A) {
     for (int r = 0; r < 4; ++r) {
       h2v[r] = tanhf(av[r] + V.b2);
       h2p[r] = tanhf(ap[r] + P.b2);
-      const float sv = row16_sum(w3v * h2v[r]);
+      const float sv = out_share(w3v, h2v[r]);
       if (i == 0) L.part[w][4 * g + r][kV] = sv;
 #pragma unroll
       for (int a = 0; a < kMaxAct; ++a) {
         if (a < na) {
-          const float sp = row16_sum(w3p[a] * h2p[r]);
+          const float sp = out_share(w3p[a], h2p[r]);
           if (i == 0) L.part[w][4 * g + r][a] = sp;
         }
       }
@@ -327,7 +274,7 @@ __global__ void __launch_bounds__(kBlock) gpd_ppo_grad_kernel(Args A) {
     // ---- per row (thread = row ri, column c; the row's 16 threads are one DPP row): c < na holds
     // mu_c, c == 8 the value
     float out = 0.0f;
-    if (c < na || c == kV) out = (((L.part[0][ri][c] + L.part[1][ri][c]) + L.part[2][ri][c]) + L.part[3][ri][c]) + b3c;
+    if (c < na || c == kV) out = out_sum(L.part, ri, c) + b3c;
     const float d = c < na ? act - out : 0.0f;
     // torch.distributions.Normal.log_prob: -((value - loc) ** 2) / (2 * var) - log(scale) - log(sqrt(2 pi))
     const float lp = c < na ? -(d * d) / (2.0f * var) - ls - 0.91893853320467274f : 0.0f;
@@ -398,53 +345,59 @@ __global__ void __launch_bounds__(kBlock) gpd_ppo_grad_kernel(Args A) {
   if (t >= 24 && t < 27) slab[O.n + t - 24] = racc;
 }
 
-// mean and unbiased std (torch .std()) of adv[idx]: two passes, every thread a strided share in
-// double, the shares added by a fixed tree: the order depends on n_rows alone
-__device__ inline double block_sum(double v, double* sh) {
+// The sum of v over threads 0 .. N - 1 of a block of kThreads, by a fixed halving tree through sh[N], in
+// every thread.  A caller that goes on to reuse sh synchronises first.
+template <typename T, int N, int kThreads = N>
+__device__ inline T block_tree_sum(T v, T* sh) {
   const int t = threadIdx.x;
-  sh[t] = v;
+  if (kThreads == N || t < N) sh[t] = v;
   __syncthreads();
-  for (int s = kStatsThreads / 2; s > 0; s >>= 1) {
+  for (int s = N / 2; s > 0; s >>= 1) {
     if (t < s) sh[t] += sh[t + s];
     __syncthreads();
   }
-  const double r = sh[0];
-  __syncthreads();
-  return r;
+  return sh[0];
 }
+
+// adv[idx] of rows r0 + u * kStatsThreads (0 past n): eight gathers in flight per thread and trip (a
+// thread's rows: t, t + 1024, ...; 16 at 16 384 rows)
+__device__ inline void gather_adv(float (&v)[kStatsBatch], int r0, int n, const int64_t* __restrict__ idx,
+                                  const float* __restrict__ adv) {
+#pragma unroll
+  for (int u = 0; u < kStatsBatch; ++u) {
+    const int r = r0 + u * kStatsThreads;
+    v[u] = r < n ? adv[idx ? idx[r] : (int64_t)r] : 0.0f;
+  }
+}
+
+// mean and unbiased std (torch .std()) of adv[idx]: two passes, every thread a strided share in
+// double, the shares added by a fixed tree: the order depends on n_rows alone
 __global__ void __launch_bounds__(kStatsThreads) gpd_ppo_adv_stats_kernel(int n, const int64_t* __restrict__ idx,
                                                                           const float* __restrict__ adv,
                                                                           float* __restrict__ head) {
   __shared__ double sh[kStatsThreads];
   const int t = threadIdx.x;
-  // eight gathers in flight per thread and trip (a thread's rows: t, t + 1024, ...; 16 at 16 384 rows)
   double s = 0.0;
   for (int r0 = t; r0 < n; r0 += kStatsBatch * kStatsThreads) {
     float v[kStatsBatch];
-#pragma unroll
-    for (int u = 0; u < kStatsBatch; ++u) {
-      const int r = r0 + u * kStatsThreads;
-      v[u] = r < n ? adv[idx ? idx[r] : (int64_t)r] : 0.0f;
-    }
+    gather_adv(v, r0, n, idx, adv);
 #pragma unroll
     for (int u = 0; u < kStatsBatch; ++u) s += (double)v[u];
   }
-  const double mean = block_sum(s, sh) / (double)n;
+  const double mean = block_tree_sum<double, kStatsThreads>(s, sh) / (double)n;
+  __syncthreads();   // sh is written again below
   double q = 0.0;
   for (int r0 = t; r0 < n; r0 += kStatsBatch * kStatsThreads) {
     float v[kStatsBatch];
-#pragma unroll
-    for (int u = 0; u < kStatsBatch; ++u) {
-      const int r = r0 + u * kStatsThreads;
-      v[u] = r < n ? adv[idx ? idx[r] : (int64_t)r] : 0.0f;
-    }
+    gather_adv(v, r0, n, idx, adv);
 #pragma unroll
     for (int u = 0; u < kStatsBatch; ++u) {
       const double d = (double)v[u] - mean;
       if (r0 + u * kStatsThreads < n) q += d * d;
     }
   }
-  const double var = block_sum(q, sh) / (double)(n - 1);   // n == 1: 0 / 0 = NaN, as torch
+  // (n == 1: 0 / 0 = NaN, as torch)
+  const double var = block_tree_sum<double, kStatsThreads>(q, sh) / (double)(n - 1);
   if (t == 0) {
     head[0] = (float)mean;
     head[1] = (float)sqrt(var) + 1e-8f;
@@ -465,13 +418,8 @@ __global__ void __launch_bounds__(256) gpd_ppo_reduce_kernel(const float* __rest
     if (e < n_params) grad[e] = s;
     else if (e < n_params + 3) head[4 + e - n_params] = s;
   }
-  sh[t] = e < n_params ? s * s : 0.0f;
-  __syncthreads();
-  for (int k = 128; k > 0; k >>= 1) {
-    if (t < k) sh[t] += sh[t + k];
-    __syncthreads();
-  }
-  if (t == 0) head[kHead + blockIdx.x] = sh[0];
+  const float sq = block_tree_sum<float, 256>(e < n_params ? s * s : 0.0f, sh);
+  if (t == 0) head[kHead + blockIdx.x] = sq;
 }
 
 __global__ void __launch_bounds__(1024) gpd_ppo_finish_kernel(int n_parts, int n_params, int n_rows, float max_grad_norm,
@@ -479,13 +427,8 @@ __global__ void __launch_bounds__(1024) gpd_ppo_finish_kernel(int n_parts, int n
                                                               float* __restrict__ stats) {
   __shared__ float sh[kNormParts];
   const int t = threadIdx.x;
-  if (t < kNormParts) sh[t] = t < n_parts ? head[kHead + t] : 0.0f;
-  __syncthreads();
-  for (int k = kNormParts / 2; k > 0; k >>= 1) {   // a fixed tree over the blocks' partial norms
-    if (t < k) sh[t] += sh[t + k];
-    __syncthreads();
-  }
-  const float sq = sh[0];
+  // a fixed tree over the blocks' partial norms
+  const float sq = block_tree_sum<float, kNormParts, 1024>(t < n_parts ? head[kHead + t] : 0.0f, sh);
   const float norm = sqrtf(sq);
   // torch clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1
   const float scale = max_grad_norm > 0.0f ? fminf(1.0f, max_grad_norm / (norm + 1e-6f)) : 1.0f;
@@ -506,18 +449,13 @@ int n_blocks(int n_rows, int max_blocks) {
 }
 int slab_stride(int n_params) { return (n_params + 3 + 3) & ~3; }
 
-template <int KQ>
-void launch(const Args& A, int grid, hipStream_t st) {
-  hipLaunchKernelGGL((gpd_ppo_grad_kernel<KQ>), dim3(grid), dim3(kBlock), 0, st, A);
-}
-
 }  // namespace
 
 extern "C" {
 
 int gpd_policy_n_params(int n_obs, int n_act) {
   if (n_obs < 1 || n_obs > GPD_POLICY_MAX_OBS || n_act < 1 || n_act > GPD_POLICY_MAX_ACT) {
-    gpd_policy_fail_(kEinval, "gpd_policy_n_params: n_obs must be in [1, 192] and n_act in [1, 8]");
+    fail(kEinval, "gpd_policy_n_params: n_obs must be in [1, 192] and n_act in [1, 8]");
     return -1;
   }
   return offsets(n_obs, n_act).n;
@@ -526,7 +464,7 @@ int gpd_policy_n_params(int n_obs, int n_act) {
 size_t gpd_policy_ppo_grad_workspace(int n_obs, int n_act, int n_rows, int max_blocks) {
   if (n_obs < 1 || n_obs > GPD_POLICY_MAX_OBS || n_act < 1 || n_act > GPD_POLICY_MAX_ACT || n_rows < 1 ||
       max_blocks < 0) {
-    gpd_policy_fail_(kEinval, "gpd_policy_ppo_grad_workspace: invalid argument");
+    fail(kEinval, "gpd_policy_ppo_grad_workspace: invalid argument");
     return 0;
   }
   const size_t slabs = (size_t)n_blocks(n_rows, max_blocks) * slab_stride(offsets(n_obs, n_act).n);
@@ -538,32 +476,31 @@ int gpd_policy_ppo_grad(const gpd_mlp_policy* p, int n_rows, const int64_t* idx,
                         float max_grad_norm, float* grad, float* stats, void* workspace, size_t workspace_bytes,
                         int max_blocks, void* stream) {
   const std::string me = "gpd_policy_ppo_grad: ";
-  if (!p) return gpd_policy_fail_(kEinval, (me + "NULL policy").c_str());
-  if (n_rows < 1) return gpd_policy_fail_(kEinval, (me + "n_rows < 1").c_str());
+  if (!p) return fail(kEinval, me + "NULL policy");
+  if (n_rows < 1) return fail(kEinval, me + "n_rows < 1");
   if (p->n_obs < 1 || p->n_obs > GPD_POLICY_MAX_OBS)
-    return gpd_policy_fail_(kEinval, (me + "n_obs must be in [1, " + std::to_string(GPD_POLICY_MAX_OBS) + "]").c_str());
+    return fail(kEinval, me + "n_obs must be in [1, " + std::to_string(GPD_POLICY_MAX_OBS) + "]");
   if (p->n_act < 1 || p->n_act > GPD_POLICY_MAX_ACT)
-    return gpd_policy_fail_(kEinval, (me + "n_act must be in [1, " + std::to_string(GPD_POLICY_MAX_ACT) + "]").c_str());
+    return fail(kEinval, me + "n_act must be in [1, " + std::to_string(GPD_POLICY_MAX_ACT) + "]");
   if (!p->pi_w1 || !p->pi_b1 || !p->pi_w2 || !p->pi_b2 || !p->pi_w3 || !p->pi_b3 || !p->vf_w1 || !p->vf_b1 ||
       !p->vf_w2 || !p->vf_b2 || !p->vf_w3 || !p->vf_b3 || !p->log_std)
-    return gpd_policy_fail_(kEinval, (me + "NULL weight").c_str());
-  if (!obs || !act || !old_logp || !adv || !ret) return gpd_policy_fail_(kEinval, (me + "NULL rollout buffer").c_str());
-  if (!grad || !stats || !workspace) return gpd_policy_fail_(kEinval, (me + "NULL grad, stats or workspace").c_str());
-  if (max_blocks < 0) return gpd_policy_fail_(kEinval, (me + "max_blocks < 0").c_str());
+    return fail(kEinval, me + "NULL weight");
+  if (!obs || !act || !old_logp || !adv || !ret) return fail(kEinval, me + "NULL rollout buffer");
+  if (!grad || !stats || !workspace) return fail(kEinval, me + "NULL grad, stats or workspace");
+  if (max_blocks < 0) return fail(kEinval, me + "max_blocks < 0");
   const size_t need = gpd_policy_ppo_grad_workspace(p->n_obs, p->n_act, n_rows, max_blocks);
   if (workspace_bytes < need)
-    return gpd_policy_fail_(kEinval, (me + "workspace holds " + std::to_string(workspace_bytes) + " bytes, " +
-                                      std::to_string(n_rows) + " rows need " + std::to_string(need)).c_str());
+    return fail(kEinval, me + "workspace holds " + std::to_string(workspace_bytes) + " bytes, " +
+                                      std::to_string(n_rows) + " rows need " + std::to_string(need));
   // the slabs are read as whole floats at any offset; 16 B keeps every slab on a float4 boundary
   if (((uintptr_t)workspace & 15) || ((uintptr_t)grad & 3) || ((uintptr_t)stats & 3) || ((uintptr_t)obs & 3) ||
       ((uintptr_t)act & 3) || ((uintptr_t)old_logp & 3) || ((uintptr_t)adv & 3) || ((uintptr_t)ret & 3) ||
       ((uintptr_t)idx & 7))
-    return gpd_policy_fail_(kEinval, (me + "misaligned pointer (workspace 16 B, idx 8 B, floats 4 B)").c_str());
+    return fail(kEinval, me + "misaligned pointer (workspace 16 B, idx 8 B, floats 4 B)");
   const Offsets O = offsets(p->n_obs, p->n_act);
   float* head = (float*)workspace;
   Args A = {};
-  A.pi = {p->pi_w1, p->pi_b1, p->pi_w2, p->pi_b2, p->pi_w3, p->pi_b3};
-  A.vf = {p->vf_w1, p->vf_b1, p->vf_w2, p->vf_b2, p->vf_w3, p->vf_b3};
+  nets_of(p, A.pi, A.vf);
   A.log_std = p->log_std;
   A.n_obs = p->n_obs; A.n_act = p->n_act; A.n_rows = n_rows;
   A.idx = idx; A.obs = obs; A.act = act; A.old_logp = old_logp; A.adv = adv; A.ret = ret;
@@ -578,13 +515,9 @@ int gpd_policy_ppo_grad(const gpd_mlp_policy* p, int n_rows, const int64_t* idx,
   const int parts = (A.stride + 255) / 256;   // <= 133 < kNormParts at n_obs = 192, n_act = 8
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(gpd_ppo_adv_stats_kernel, dim3(1), dim3(kStatsThreads), 0, st, n_rows, idx, adv, head);
-  const int kq = (p->n_obs + 3) / 4;
-  if (kq <= 8) launch<8>(A, grid, st);
-  else if (kq <= 16) launch<16>(A, grid, st);
-  else if (kq <= 18) launch<18>(A, grid, st);
-  else if (kq <= 24) launch<24>(A, grid, st);
-  else if (kq <= 36) launch<36>(A, grid, st);
-  else launch<GPD_POLICY_MAX_OBS / 4>(A, grid, st);
+  with_kq((p->n_obs + 3) / 4, [&](auto kq) {
+    hipLaunchKernelGGL((gpd_ppo_grad_kernel<decltype(kq)::value>), dim3(grid), dim3(kBlock), 0, st, A);
+  });
   hipLaunchKernelGGL(gpd_ppo_reduce_kernel, dim3(parts), dim3(256), 0, st, A.slabs, grid, A.stride, O.n, grad, head);
   hipLaunchKernelGGL(gpd_ppo_finish_kernel, dim3(1), dim3(1024), 0, st, parts, O.n, n_rows, max_grad_norm, grad, head,
                      stats);

@@ -30,9 +30,7 @@ PARAM_NAMES = ("pi_w1", "pi_b1", "pi_w2", "pi_b2", "pi_w3", "pi_b3", "vf_w1", "v
 
 
 class MlpPolicyStruct(ctypes.Structure):
-    _fields_ = [("n_obs", ctypes.c_int), ("n_act", ctypes.c_int)] + [
-        (n, ctypes.c_void_p) for n in ("pi_w1", "pi_b1", "pi_w2", "pi_b2", "pi_w3", "pi_b3",
-                                       "vf_w1", "vf_b1", "vf_w2", "vf_b2", "vf_w3", "vf_b3", "log_std")]
+    _fields_ = [("n_obs", ctypes.c_int), ("n_act", ctypes.c_int)] + [(n, ctypes.c_void_p) for n in PARAM_NAMES]
 
 
 _lib = None
@@ -112,6 +110,17 @@ def _module_struct(module):
     return st, params, n_obs, n_act, dev
 
 
+def _ptr(t, name, dtype, device=None, numel=None):
+    """The address of ``t``, a contiguous ``dtype`` tensor on the GPU (on ``device``, if given), optionally of
+    ``numel`` = (rows, width) elements."""
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous()) or (device is not None and t.device != device):
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor on {device}" if device is not None else
+                         f"{name} must be a contiguous float32 device tensor")
+    if numel is not None and t.numel() != numel[0] * numel[1]:
+        raise ValueError(f"{name} must hold {numel[0]} x {numel[1]} elements, has {t.numel()}")
+    return ctypes.c_void_p(t.data_ptr())
+
+
 def _as_int64(x):
     """``x`` mod 2^64 as the int64 with the same bits (the device words are uint64, torch's int64)."""
     x = int(x) & 0xFFFFFFFFFFFFFFFF
@@ -162,13 +171,7 @@ class MlpPolicyKernel:
         self.rng[2:] = int(n)
 
     def _rows(self, t, width, name):
-        if t is None:
-            return None
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous float32 device tensor")
-        if t.numel() != self._n * width:
-            raise ValueError(f"{name} must hold {self._n} x {width} elements, has {t.numel()}")
-        return ctypes.c_void_p(t.data_ptr())
+        return None if t is None else _ptr(t, name, torch.float32, numel=(self._n, width))
 
     def step(self, obs=None, act_env=None, buf_obs=None, buf_act=None, buf_logp=None, buf_val=None,
              deterministic=False, prev=None, gamma=0.99, buf_rew=None, buf_done=None, n_rows=None):
@@ -253,9 +256,7 @@ class PpoGradKernel:
             p.grad = v
 
     def _buf(self, t, name, dtype=torch.float32):
-        if not (t.is_cuda and t.device == self.device and t.dtype == dtype and t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous {dtype} tensor on {self.device}")
-        return ctypes.c_void_p(t.data_ptr())
+        return _ptr(t, name, dtype, self.device)
 
     def grad_step(self, idx, obs, act, logp, adv, ret, clip, vf_coef, max_grad_norm, n_rows=None):
         """One minibatch: rows ``idx`` (int64 device tensor, or None for rows 0 .. n_rows - 1) of the

@@ -1,5 +1,5 @@
 /*
- * gpd_policy.h — C ABI of the fused rollout policy (libgpd_policy.so, csrc/gpd_policy.hip).
+ * gpd_policy.h — C ABI of the fused rollout policy (libgpd_policy.so, csrc/policy/gpd_policy.hip).
  *
  * The caller side of the hot path: the reference trains stable-baselines3 PPO
  * ('MlpPolicy', examples/learn.py:52-94), whose rollout (SB3 OnPolicyAlgorithm.collect_rollouts)
@@ -71,7 +71,7 @@ int gpd_policy_rollout_step(const gpd_mlp_policy* policy, int n_rows, const floa
 int gpd_policy_gae(int n_steps, int n_rows, const float* rew, const float* val, const float* done,
                    const float* last_val, double gamma, double lam, float* adv, float* ret, void* stream);
 
-/* The PPO minibatch gradient (csrc/gpd_ppo_grad.hip): loss, backward and gradient-norm clip of
+/* The PPO minibatch gradient (csrc/policy/gpd_ppo_grad.hip): loss, backward and gradient-norm clip of
  * examples/learn.py's minibatch step, up to the optimizer.
  *   mu = pi(obs), scale = exp(log_std)
  *   logp  = sum_a [-(act - mu)^2 / (2 scale^2) - log_std - log sqrt(2 pi)]

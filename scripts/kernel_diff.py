@@ -1,10 +1,12 @@
 #!/usr/bin/env python
-"""Compare the device assembly of csrc/gpd.hip between two trees, kernel by kernel (CPU only).
+"""Compare the device assembly of a library between two trees, kernel by kernel (CPU only).
 
-    python scripts/kernel_diff.py OLD NEW [-o table.txt]
+    python scripts/kernel_diff.py [--policy] OLD NEW [-o table.txt]
 
 OLD and NEW are each a checkout of this repository (its gpd.hip is cross-compiled to device
-assembly with the flags of _build.build()) or a .s file made that way.  Per kernel symbol the
+assembly with the flags of _build.build(); with --policy every unit of libgpd_policy.so, named as
+_build.POLICY_UNITS names them and found under csrc/policy/ or, in a tree from before the move,
+under csrc/, with the flags of _build.build_policy()) or a .s file made that way.  Per kernel symbol the
 table says whether the two bodies are identical once comments are stripped and local labels are
 renumbered, and lists VGPRs, SGPRs, scratch bytes, static LDS, code length and occupancy as the
 assembler reports them.  Whole bodies are compared; nothing looks inside them.
@@ -25,15 +27,33 @@ FIELDS = (("vgpr", "NumVgprs"), ("agpr", "NumAgprs"), ("sgpr", "TotalNumSgprs"),
           ("lds", "LDSByteSize"), ("code", "codeLenInByte"), ("occ", "Occupancy"))
 
 
-def device_asm(src, out):
-    """The device assembly of a tree, compiled to `out` (or the text of the .s file given)."""
+def units(src, policy):
+    """The translation units of the library in the tree `src`."""
+    csrc = src / PKG / "csrc"
+    if not policy:
+        return [csrc / "gpd.hip"]
+    found = []
+    for u in _build.POLICY_UNITS:
+        where = [d / u.name for d in (csrc / "policy", csrc) if (d / u.name).exists()]
+        if not where:
+            raise SystemExit(f"{src}: no {u.name} under {csrc / 'policy'} or {csrc}")
+        found.append(where[0])
+    return found
+
+
+def device_asm(src, out, policy=False):
+    """The device assembly of a tree, compiled to `out`.N.s (or the text of the .s file given)."""
     src = pathlib.Path(src)
     if not src.is_dir():
         return src.read_text()
-    cmd = [_build.hipcc()] + _build.DEVICE_FLAGS + [f"-I{src / 'include'}", "--cuda-device-only", "-S", "-o", str(out),
-                                                    str(src / PKG / "csrc" / "gpd.hip")]
-    subprocess.run(cmd, check=True)
-    return pathlib.Path(out).read_text()
+    flags = _build.POLICY_FLAGS if policy else _build.DEVICE_FLAGS
+    text = ""
+    for n, unit in enumerate(units(src, policy)):
+        asm = pathlib.Path(f"{out}.{n}.s")
+        subprocess.run([_build.hipcc()] + flags + [f"-I{src / 'include'}", "--cuda-device-only", "-S", "-o", str(asm),
+                                                   str(unit)], check=True)
+        text += asm.read_text()
+    return text
 
 
 def kernels(asm):
@@ -75,7 +95,7 @@ def demangle(names):
 
 
 def short(name):
-    name = re.sub(r"^void gpd::", "", name)
+    name = re.sub(r"^(void )?(gpd|\(anonymous namespace\))::", "", name)
     return re.sub(r"\(.*$", "", name)
 
 
@@ -84,9 +104,11 @@ def main():
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("-o", "--out", help="also write the table to this file")
+    ap.add_argument("--policy", action="store_true", help="compare libgpd_policy.so's units instead of gpd.hip")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
-        old, new = (kernels(device_asm(src, pathlib.Path(tmp) / f"{i}.s")) for i, src in enumerate((args.old, args.new)))
+        old, new = (kernels(device_asm(src, pathlib.Path(tmp) / str(i), args.policy))
+                    for i, src in enumerate((args.old, args.new)))
     pretty = demangle(sorted(set(old) | set(new)))
     cols = [k for k, _ in FIELDS]
     rows = [f"{'kernel':<72} {'body':<9} " + " ".join(f"{c:>13}" for c in cols)]

@@ -1,4 +1,4 @@
-"""The fused rollout policy (libgpd_policy.so, csrc/gpd_policy.hip) against the torch forward it
+"""The fused rollout policy (libgpd_policy.so, csrc/policy/gpd_policy.hip) against the torch forward it
 replaces: examples/learn.py's ActorCritic (SB3 MlpPolicy: separate 64-64 tanh actor and critic,
 state-independent log-std; the reference's caller examples/learn.py:52-94).
 

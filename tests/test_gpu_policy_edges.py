@@ -1,4 +1,4 @@
-"""The fused rollout policy kernel (csrc/gpd_policy.hip) against tests/policy_ref.py, a float64 host
+"""The fused rollout policy kernel (csrc/policy/gpd_policy.hip) against tests/policy_ref.py, a float64 host
 restatement of gpd_policy_rollout_step, at the shapes and modes where the kernel takes another path.
 
 What pins the kernel here:

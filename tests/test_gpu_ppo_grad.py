@@ -1,4 +1,4 @@
-"""The PPO minibatch gradient kernel (gpd_policy_ppo_grad, csrc/gpd_ppo_grad.hip; policy.PpoGradKernel)
+"""The PPO minibatch gradient kernel (gpd_policy_ppo_grad, csrc/policy/gpd_ppo_grad.hip; policy.PpoGradKernel)
 against torch float64 autograd of examples/learn.py's minibatch loss and tests/ppo_grad_ref.py.
 
 The parity gate is relative to torch itself: per tensor, err = max |g - g64| / max |g64|; e32 is that

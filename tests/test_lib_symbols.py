@@ -75,15 +75,47 @@ def test_policy_library_host_checks():
     st = policy.MlpPolicyStruct()
     st.n_obs, st.n_act = 72, 4
     fake = 256          # never dereferenced: every call below fails its host-side checks
-    for n in ("pi_w1", "pi_b1", "pi_w2", "pi_b2", "pi_w3", "pi_b3", "vf_w1", "vf_b1", "vf_w2", "vf_b2", "vf_w3",
-              "vf_b3", "log_std"):
+    for n in policy.PARAM_NAMES:
         setattr(st, n, fake)
     vp = ctypes.c_void_p
-    rc = pl.gpd_policy_rollout_step(ctypes.byref(st), 100, vp(fake), vp(fake), None, vp(fake), None, None, 0,
-                                    vp(fake), 6, None, None, None, None, 0.99, None, None, None)
-    assert rc == -1 and b"row-group counters" in pl.gpd_policy_last_error()
-    assert pl.gpd_policy_rollout_step(None, 100, None, None, None, None, None, None, 0, None, 0, None, None, None,
-                                      None, 0.99, None, None, None) == -1
+
+    def refused(code, msg, policy_=st, n_rows=100, obs=fake, buf_act=fake, deterministic=0, rng=fake, rng_groups=7,
+                prev=(None,) * 4, outs=(None, None)):
+        rc = pl.gpd_policy_rollout_step(
+            ctypes.byref(policy_) if policy_ is not None else None, n_rows, vp(obs) if obs else None, None, None,
+            vp(buf_act) if buf_act else None, None, None, deterministic, vp(rng) if rng else None, rng_groups,
+            *(vp(p) if p else None for p in prev), 0.99, *(vp(o) if o else None for o in outs), None)
+        assert rc == code
+        assert pl.gpd_policy_last_error() == b"gpd_policy_rollout_step: " + msg, pl.gpd_policy_last_error()
+
+    def variant(**fields):
+        v = policy.MlpPolicyStruct()
+        ctypes.memmove(ctypes.byref(v), ctypes.byref(st), ctypes.sizeof(st))
+        for n, x in fields.items():
+            setattr(v, n, x)
+        return v
+
+    refused(-1, b"NULL policy", policy_=None)
+    refused(-1, b"n_rows < 1", n_rows=0)
+    refused(-4, b"n_obs must be in [1, 192]", policy_=variant(n_obs=policy.MAX_OBS + 1))
+    refused(-4, b"n_obs must be in [1, 192]", policy_=variant(n_obs=0))
+    refused(-4, b"n_act must be in [1, 8]", policy_=variant(n_act=policy.MAX_ACT + 1))
+    refused(-4, b"n_act must be in [1, 8]", policy_=variant(n_act=0))
+    # the range comes before the weights, the critic's before the actor's
+    refused(-4, b"n_obs must be in [1, 192]", policy_=variant(n_obs=0, vf_w1=None))
+    refused(-1, b"NULL critic weight", policy_=variant(vf_w2=None))
+    refused(-1, b"NULL critic weight", policy_=variant(vf_b3=None, pi_w1=None))
+    refused(-1, b"NULL actor weight", policy_=variant(pi_w3=None))
+    refused(-1, b"NULL actor weight", policy_=variant(log_std=None))
+    refused(-1, b"sampling needs the rng state", rng=None)
+    refused(-1, b"rng holds 6 row-group counters, sampling 100 rows needs 7", rng_groups=6)
+    refused(-1, b"the bootstrap needs terminated, truncated, terminal_obs, buf_rew and buf_done",
+            prev=(fake, fake, None, fake), outs=(fake, fake))
+    refused(-1, b"the bootstrap needs terminated, truncated, terminal_obs, buf_rew and buf_done",
+            prev=(fake,) * 4, outs=(fake, None))
+    refused(-1, b"nothing to do (obs and reward NULL)", obs=None)
+    # a critic-only call needs neither the actor's weights nor the rng: it gets as far as "nothing to do"
+    refused(-1, b"nothing to do (obs and reward NULL)", policy_=variant(pi_w1=None, log_std=None), obs=None, rng=None)
 
 
 @pytest.mark.parametrize("E,D,W", [(4096, 1, 72), (3, 1, 72), (5, 2, 27), (1, 8, 36), (4095, 3, 27)])
