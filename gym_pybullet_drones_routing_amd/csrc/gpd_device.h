@@ -1403,6 +1403,44 @@ __device__ __forceinline__ void dyn_substep(Drone<R>& s, R rpm[4], R W[4], R las
 // Rate half: ω' = ω + dt J⁻¹(τ − ω×Jω) (:852-856) and the weights of _integrateQ(q, ω', dt)
 // (:876-889): h = {cos θ, sin θ/|ω'|, p, q, r} with (p, q, r) = ω' above the np.isclose threshold
 // and 0 below it (then cos θ = 1 exactly: the pose half's update returns q/|q|).
+// It comes in two pieces: only the recurrence ω -> ω' feeds the next substep, the weights feed
+// only the hand-off, so step_kernel_duo's f64 loop publishes the weights of substep k and runs the
+// recurrence of substep k+1 behind the LDS writes.
+template <typename R>
+__device__ __forceinline__ void rate_recur(R& wx, R& wy, R& wz, const R W[4], const DynK<R>& k) {
+  const R jwx = k.jx * wx, jwy = k.jy * wy, jwz = k.jz * wz;
+  const R cx = wy * jwz - wz * jwy;
+  const R cy = wz * jwx - wx * jwz;
+  const R cz = wx * jwy - wy * jwx;
+  const R dwx = k.ijx * (W[1] - cx), dwy = k.ijy * (W[2] - cy), dwz = k.ijz * (W[3] - cz);
+  wx = wx + k.dt * dwx;
+  wy = wy + k.dt * dwy;
+  wz = wz + k.dt * dwz;
+}
+// The weights of ω' by the series; `big` (|θ| >= 0.5) lanes are fixed up by rate_weights_big.
+template <typename R>
+__device__ __forceinline__ bool rate_weights(R wx, R wy, R wz, const DynK<R>& k, R h[5], R& n2) {
+  n2 = wx * wx + wy * wy + wz * wz;
+  const bool rot = n2 > R(1e-16);
+  const R t2 = n2 * k.hdt2;
+  R co, sc;
+  cos_sinc(t2, co, sc);
+  h[0] = co; h[1] = k.hdt * sc;
+  h[2] = rot ? wx : R(0); h[3] = rot ? wy : R(0); h[4] = rot ? wz : R(0);
+  return t2 >= R(0.25);
+}
+template <typename R>
+__device__ __forceinline__ void rate_weights_big(bool big, R n2, const DynK<R>& k, R h[5]) {
+  if (GPD_RARE(__ballot(big) != 0ull)) {
+    if (big) {
+      const CoSh<R> cs = cold_cos_sinc(n2, k.hdt);
+      h[0] = cs.co;
+      h[1] = cs.sh;
+    }
+  }
+}
+// The whole rate half, which the f32 kernels keep.  (Written as the three pieces in a row the f32
+// kernels compile to other instructions, so it repeats their lines and must stay in step with them.)
 template <typename R>
 __device__ __forceinline__ void rate_half(R& wx, R& wy, R& wz, const R W[4], const DynK<R>& k, R h[5]) {
   const R jwx = k.jx * wx, jwy = k.jy * wy, jwz = k.jz * wz;
@@ -1475,6 +1513,39 @@ __device__ __forceinline__ void pose_half(Drone<R>& s, R fz, const R h[5], const
     s.ay = (Rm[3] * w[0] + Rm[4] * w[1]) + Rm[5] * w[2];
     s.az = (Rm[6] * w[0] + Rm[7] * w[1]) + Rm[8] * w[2];
   }
+}
+
+// The step's final readback with the root of |q|^2 taken only by a wave that holds a lane outside
+// UnitTol (readback_core evaluates it on every lane and selects): after the substeps no lane is.
+// The unit lanes get readback_core's bits (the state after 60 steps is bit-identical).  The other
+// side is defensive: pose_half<CHECK> re-normalises in a step's first substep, so no test reaches
+// it.  The matrix and sign lines repeat readback_core's and must stay in step with them
+// (readback_core serves the one-wave kernels and is left alone).  step_kernel_duo's.
+template <typename R>
+__device__ __forceinline__ void readback_fused_rare(R x, R y, R z, R w, R qn[4], R m[9]) {
+  const R d = x * x + y * y + z * z + w * w;
+  const bool unit = g_abs(d - R(1)) < UnitTol<R>::v;
+  R inv0 = R(1.5) - R(0.5) * d;
+  R s = R(2) * (R(2) - d);
+  if (GPD_RARE(__ballot(!unit) != 0ull)) {
+    if (!unit) {
+      const R invr = g_rsqrt(d);
+      inv0 = invr;
+      s = R(2) * (invr * invr);
+    }
+  }
+  const R xs = x * s, ys = y * s, zs = z * s;
+  const R wx = w * xs, wy = w * ys, wz = w * zs;
+  const R xx = x * xs, xy = x * ys, xz = x * zs;
+  const R yy = y * ys, yz = y * zs, zz = z * zs;
+  m[0] = R(1) - (yy + zz); m[1] = xy - wz;           m[2] = xz + wy;
+  m[3] = xy + wz;          m[4] = R(1) - (xx + zz);  m[5] = yz - wx;
+  m[6] = xz - wy;          m[7] = yz + wx;           m[8] = R(1) - (xx + yy);
+  const R trace = m[0] + m[4] + m[8];
+  const R kd = m[0] < m[4] ? (m[4] < m[8] ? z : y) : (m[0] < m[8] ? z : x);
+  const R key = trace > R(0) ? w : kd;
+  const R inv = key < R(0) ? -inv0 : inv0;
+  qn[0] = x * inv; qn[1] = y * inv; qn[2] = z * inv; qn[3] = w * inv;
 }
 
 // Summed downwash on drone (px,py,pz) from the env's D drones whose positions sit in LDS

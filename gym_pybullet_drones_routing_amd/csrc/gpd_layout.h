@@ -24,9 +24,11 @@ enum : int { TASK_NONE = 0, TASK_HOVER = 1, TASK_MULTIHOVER = 2 };
 // shader clock at phase boundaries of step_kernel into g_stamps[block][phase].  The shipped
 // library executes no stamp.
 #ifdef GPD_STAMPS
-constexpr int kStampPhases = 24;   // 0..10 shader clocks; 11 / 12: s_memrealtime (100 MHz) at entry / end;
+constexpr int kStampPhases = 88;   // 0..10 shader clocks; 11 / 12: s_memrealtime (100 MHz) at entry / end;
                                    // 13: rate / io wave end (realtime); 14..16: HW_ID of waves 0..2;
-                                   // 17..23: io wave phases (shader clocks)
+                                   // 17..23: io wave phases (shader clocks);
+                                   // 24 + 16 w + k: hand-off barrier k < 16 of step_kernel_duo (shader clocks),
+                                   // w = 0 / 1 the rate wave's arrival / release, 2 / 3 the pose wave's
 __device__ unsigned long long g_stamps[65536 * kStampPhases];
 #define GPD_STAMP(k)                                                                      \
   do {                                                                                    \
@@ -51,7 +53,17 @@ __device__ unsigned long long g_stamps[65536 * kStampPhases];
     if (tid == 0 && blockIdx.x < 65536) g_stamps[blockIdx.x * kStampPhases + 17 + (k)] = t_; \
     __builtin_amdgcn_sched_barrier(0);                                                    \
   } while (0)
+// (lane 0 of the calling wave; the arrival stamp sits in front of lds_barrier's own lgkmcnt(0))
+#define GPD_HSTAMP(w, k)                                                                  \
+  do {                                                                                    \
+    __builtin_amdgcn_sched_barrier(0);                                                    \
+    const unsigned long long t_ = __builtin_amdgcn_s_memtime();                           \
+    if (tid == 0 && blockIdx.x < 65536 && (k) < 16)                                       \
+      g_stamps[blockIdx.x * kStampPhases + 24 + 16 * (w) + (k)] = t_;                     \
+    __builtin_amdgcn_sched_barrier(0);                                                    \
+  } while (0)
 #else
+#define GPD_HSTAMP(w, k) do {} while (0)
 #define GPD_IOSTAMP(k) do {} while (0)
 #define GPD_STAMP(k) do {} while (0)
 #define GPD_RSTAMP(k) do {} while (0)

@@ -39,6 +39,10 @@ __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R*
   v.state = state_p; v.ctr = ctr_p; v.npad = npad_p; v.N = n_p; v.tpb = tpb_p;
   io.actions = actions_p;
   constexpr int A = act_width(ACT);
+  // The f64 kernels run the substep loop in the order described at the two waves below.  The f32
+  // kernels keep the plain order: hipcc packs and contracts the moved f32 expressions differently,
+  // which changes last bits of their results.
+  constexpr bool kAhead = sizeof(R) == 8;
   extern __shared__ float4 tile4[];
   float* tilef = reinterpret_cast<float*>(tile4);
   __shared__ R shand[2][5][kWave];        // rate_half -> pose_half, by substep parity
@@ -294,13 +298,53 @@ __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R*
 #pragma unroll
     for (int k = 0; k < 4; ++k) rpm[k] = (R)action_to_rpm(dk.hover_f32, a[A == 4 ? k : 0]);
     rpm_wrench<R, 0>(rpm, dk, c, W);
-    for (int k = 0; k < nsub; ++k) {
-      R h[5];
-      rate_half(wx, wy, wz, W, dk, h);
+    if constexpr (kAhead) {
+      // The recurrence runs one substep ahead of its weights.  Only ω_{k+1} -> ω_{k+2} (6 levels)
+      // feeds the next substep; the weights of ω_{k+1} (9 levels) feed only the hand-off.  So the
+      // wave publishes the weights first and runs the recurrence behind the LDS writes, on their
+      // way to the barrier, where it covers the write acknowledgement.  The cost is at hand-off 0,
+      // which two recurrence steps now precede: the rate wave reaches it ~200 cycles later (stamps:
+      // 1 975 against 1 774) and the pose wave waits 270 there.  Hand-offs 1..6 come 15-30 cycles
+      // sooner each and the last one, which no longer holds a recurrence, 240 sooner (536 against
+      // 780 cycles), so hand-off 7 is reached ~100 cycles earlier.  (The two chains interleaved in
+      // one block in front of the writes measured no gain: profiles/r8/substep_schedule/.)  The
+      // last substep has no look-ahead: sw[] receives ω_nsub, no step past nsub is evaluated.
+      rate_recur(wx, wy, wz, W, dk);   // ω_1
+      for (int k = 0; k < nsub - 1; ++k) {
+        R h[5], n2;
+        const R cx = wx, cy = wy, cz = wz;   // ω_{k+1}
+        const bool big = rate_weights(cx, cy, cz, dk, h, n2);
+        rate_weights_big(big, n2, dk, h);
 #pragma unroll
-      for (int j = 0; j < 5; ++j) shand[k & 1][j][tid] = h[j];
-      if (k == nsub - 1) { sw[0][tid] = wx; sw[1][tid] = wy; sw[2][tid] = wz; }
-      lds_barrier();   // hand-off k published
+        for (int j = 0; j < 5; ++j) shand[k & 1][j][tid] = h[j];
+        rate_recur(wx, wy, wz, W, dk);       // ω_{k+2}
+        asm volatile("" : "+v"(wx), "+v"(wy), "+v"(wz));   // (complete in front of the barrier)
+        GPD_HSTAMP(0, k);
+        lds_barrier();   // hand-off k published
+        GPD_HSTAMP(1, k);
+      }
+      {
+        R h[5], n2;
+        const bool big = rate_weights(wx, wy, wz, dk, h, n2);
+        rate_weights_big(big, n2, dk, h);
+#pragma unroll
+        for (int j = 0; j < 5; ++j) shand[(nsub - 1) & 1][j][tid] = h[j];
+        sw[0][tid] = wx; sw[1][tid] = wy; sw[2][tid] = wz;
+        GPD_HSTAMP(0, nsub - 1);
+        lds_barrier();   // last hand-off and the final rates published
+        GPD_HSTAMP(1, nsub - 1);
+      }
+    } else {
+      for (int k = 0; k < nsub; ++k) {
+        R h[5];
+        rate_half(wx, wy, wz, W, dk, h);
+#pragma unroll
+        for (int j = 0; j < 5; ++j) shand[k & 1][j][tid] = h[j];
+        if (k == nsub - 1) { sw[0][tid] = wx; sw[1][tid] = wy; sw[2][tid] = wz; }
+        GPD_HSTAMP(0, k);
+        lds_barrier();   // hand-off k published
+        GPD_HSTAMP(1, k);
+      }
     }
     if (IO) {          // the io wave owns the history columns and the ring append
       lds_barrier();   // final
@@ -390,19 +434,25 @@ __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R*
     for (int j = 0; j < 5; ++j) h[j] = shand[k & 1][j][tid];
   };
   if (nsub > 1) {
+    GPD_HSTAMP(2, 0);
     lds_barrier();   // hand-off 0
+    GPD_HSTAMP(3, 0);
     R h[5];
     hand_off(0, h);
     pose_half<R, false, true>(s, fz, h, wnone, dk);
     GPD_STAMP(1);
     for (int k = 1; k < nsub - 1; ++k) {
+      GPD_HSTAMP(2, k);
       lds_barrier();   // hand-off k
+      GPD_HSTAMP(3, k);
       hand_off(k, h);
       pose_half<R, false, false>(s, fz, h, wnone, dk);
     }
   }
   {
+    GPD_HSTAMP(2, nsub - 1);
     lds_barrier();   // last hand-off + final rates
+    GPD_HSTAMP(3, nsub - 1);
     R h[5];
     hand_off(nsub - 1, h);
     s.wx = sw[0][tid]; s.wy = sw[1][tid]; s.wz = sw[2][tid];
@@ -413,7 +463,8 @@ __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R*
   GPD_STAMP(2);
   // final readback (:374) -> obs / reward / done
   R qn[4], Rm[9];
-  readback_fused(s.qx, s.qy, s.qz, s.qw, qn, Rm);
+  if constexpr (kAhead) readback_fused_rare(s.qx, s.qy, s.qz, s.qw, qn, Rm);
+  else readback_fused(s.qx, s.qy, s.qz, s.qw, qn, Rm);
   AttitudeArgs<R> att = attitude_args(qn);
   bool tilted, up_unused;   // |roll| or |pitch| > 0.4, decided exactly near the limit (attitude_decide)
   attitude_decide<R, true, false>(s.qx, s.qy, s.qz, s.qw, att, tilted, up_unused);

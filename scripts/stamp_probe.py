@@ -24,7 +24,7 @@ for prec in os.environ.get("STAMP_PRECS", "f64 f32").split():
         for _ in range(4): g.replay()
         torch.cuda.synchronize()
         nb = min(65536, -(-sim.n_drones // sim.constants.drones_per_block))
-        buf = np.zeros((nb, 24), np.uint64)
+        buf = np.zeros((nb, 88), np.uint64)
         assert lib.gpd_debug_stamps(buf.ctypes.data_as(ctypes.c_void_p), nb) == 0
         t = buf.astype(np.int64)
         order = [0, 10, 1, 2, 3, 4, 5, 6, 8, 9, 7]   # 10: loads landed; 8/9 inside the copy-out (after LDS reads, after stores)
@@ -53,6 +53,23 @@ for prec in os.environ.get("STAMP_PRECS", "f64 f32").split():
                   " ".join(f"{names[j + 1]}:{dd[j + 1]}" for j in range(5)) +
                   f" | io B0 arrive -> pose stamp1 {int(np.median(t[:, 1] - io[:, 0]))}"
                   f" | io final arrive vs pose stamp5 {int(np.median(io[:, 4] - t[:, 5]))}", flush=True)
+        if sim.constants.lanes_per_block >= 128 and t[:, 24].min() > 0:
+            # hand-off barrier k of step_kernel_duo: arrival / release of the rate wave (24 + k, 40 + k) and of
+            # the pose wave (56 + k, 72 + k); who arrives last, by how much, and each wave's barrier-to-barrier time
+            ns = min(16, sim.constants.pyb_steps_per_ctrl)
+            ra, rr, pa, pr = (t[:, 24 + 16 * w:24 + 16 * w + ns] for w in range(4))
+            med = lambda x: int(np.median(x))
+            print("    hand-offs (cycles, median over blocks; arrivals relative to the pose wave's entry stamp 0):", flush=True)
+            print("      k  rate_arr  pose_arr  rate-pose  last   release-last_arrival  rate:rel(k-1)->arr(k)  pose:rel(k-1)->arr(k)",
+                  flush=True)
+            for k in range(ns):
+                late = ra[:, k] - pa[:, k]
+                rel = np.maximum(rr[:, k], pr[:, k]) - np.maximum(ra[:, k], pa[:, k])
+                rw = med(ra[:, k] - rr[:, k - 1]) if k else med(ra[:, 0] - t[:, 0])
+                pw = med(pa[:, k] - pr[:, k - 1]) if k else med(pa[:, 0] - t[:, 0])
+                print(f"      {k}  {med(ra[:, k] - t[:, 0]):8d}  {med(pa[:, k] - t[:, 0]):8d}  {med(late):9d}  "
+                      f"{'rate' if med(late) > 0 else 'pose'}  {med(rel):8d}  {rw:8d}  {pw:8d}   "
+                      f"(rate last in {float((late > 0).mean()):.2f} of blocks)", flush=True)
         hw = t[:, 14:14 + sim.constants.lanes_per_block // 64]
         simd = (hw >> 4) & 3
         same = [(simd[:, a] == simd[:, b]).mean() for a in range(simd.shape[1]) for b in range(a + 1, simd.shape[1])]
