@@ -35,7 +35,8 @@ GPD_CMD_RPM, GPD_CMD_VEL, GPD_CMD_WAYPOINT = 0, 1, 2
 
 # Every symbol include/gpd.h declares (checked by tests/test_lib_symbols.py).
 EXPORTED = ("gpd_abi_version", "gpd_last_error", "gpd_default_params", "gpd_create", "gpd_destroy",
-            "gpd_get_constants", "gpd_reset", "gpd_step", "gpd_step_seq", "gpd_integrate", "gpd_get_state20",
+            "gpd_get_constants", "gpd_reset", "gpd_step", "gpd_step_seq", "gpd_step_seq_plan", "gpd_integrate",
+            "gpd_get_state20",
             "gpd_get_raw_state", "gpd_set_raw_state", "gpd_get_step_counters",
             "gpd_set_step_counters", "gpd_state_bytes", "gpd_save_state", "gpd_load_state",
             "gpd_default_pid_params", "gpd_set_pid_params", "gpd_set_pid_gains", "gpd_get_pid_gains",
@@ -132,6 +133,7 @@ def load():
         "gpd_reset": (ci, [vp, vp, vp, vp]),
         "gpd_step": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
         "gpd_step_seq": (ci, [vp, vp, ci, ci, vp, vp, vp, vp, vp, vp]),
+        "gpd_step_seq_plan": (ci, [vp, ci]),
         "gpd_integrate": (ci, [vp, vp, i, vp, vp]),
         "gpd_get_state20": (ci, [vp, vp, vp]),
         "gpd_get_raw_state": (ci, [vp, vp, vp]),

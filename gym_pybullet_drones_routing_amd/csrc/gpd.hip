@@ -330,6 +330,26 @@ const void* step_kernel_fn(const gpd_sim* s) {
   return step_fn<R>(act, multi, pf, s->stream);
 }
 
+// gpd_step_seq's fused form (step_seq_kernel, gpd_step_seq.h): the sims whose step is
+// step_kernel_duo<R, ACT, true>, one launch per kSeqStepsPerLaunch steps (gpd_cmd_rollout's default).
+// f64 only: hipcc contracts the f32 instantiation's multiply-adds differently from the per-step
+// kernel's (observations differ in last bits after 40 steps), so f32 sims keep the per-step loop
+// and the f32 kernel is not built.
+constexpr int kSeqStepsPerLaunch = 256;
+inline bool seq_fused(const gpd_sim* s) { return s->duo && s->step_waves == 3 && s->prec == GPD_F64; }
+template <typename R>
+const void* step_seq_fn(const gpd_sim* s) {
+  if constexpr (sizeof(R) == 8)
+    return with_rpm_act(s->cfg.act_type, [](auto a) { return (const void*)step_seq_kernel<R, decltype(a)::value>; });
+  else
+    return nullptr;
+}
+// the launches gpd_step_seq issues for n_steps steps
+inline int step_seq_launches(const gpd_sim* s, int n_steps) {
+  if (n_steps <= 0) return 0;
+  return seq_fused(s) && n_steps >= 2 ? (n_steps + kSeqStepsPerLaunch - 1) / kSeqStepsPerLaunch : n_steps;
+}
+
 // static LDS of the run-time-flag step kernel of an action type (the one-wave kernel every sim
 // that is not wide can fall back to: upload_tables)
 template <typename R>
@@ -368,8 +388,11 @@ int prepare_step_kernel(gpd_sim* s) {
     return fail(GPD_EUNSUPPORTED, "gpd_create: ctrl_freq too high for drone <-> drone contact (observation tile + "
                                   "the step kernel's LDS exceed 160 KiB; GPD_F_NO_DRONE_CONTACT lifts the limit)");
   // the observation tile can exceed the 64 KiB default dynamic-LDS limit for long histories
-  if (s->tile_bytes > 65536)
+  if (s->tile_bytes > 65536) {
     HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, s->tile_bytes));
+    if (seq_fused(s))   // gpd_step_seq's fused kernel keeps its action history in the same tile
+      HIP_TRY(hipFuncSetAttribute(step_seq_fn<R>(s), hipFuncAttributeMaxDynamicSharedMemorySize, s->tile_bytes));
+  }
   return GPD_OK;
 }
 
@@ -477,6 +500,28 @@ int launch_step(gpd_sim* s, const float* actions, float* obs, float* reward, uin
   hipLaunchKernelGGL(f, dim3(grid), dim3(s->step_waves * kWave), lds, st, v.state, io.actions, v.ctr, c, v.npad,
                      v.N, v.tpb, v, io);
   HIP_TRY(hipGetLastError());
+  return GPD_OK;
+}
+
+// n_steps >= 2 steps of a seq_fused sim: step t reads slot (t % n_slots) of actions
+template <typename R>
+int launch_step_seq(gpd_sim* s, const float* actions, int n_slots, int n_steps, float* obs, float* reward,
+                    uint8_t* term, uint8_t* trunc, float* terminal_obs, hipStream_t st) {
+  StepIO<R> io;
+  io.actions = actions; io.obs = obs; io.reward = reward; io.term = term; io.trunc = trunc;
+  io.terminal_obs = terminal_obs;
+  const SimView<R> v = make_view<R>(s);
+  const Consts<R>* c = (const Consts<R>*)s->d_consts;
+  typedef void (*SeqFn)(R*, const float*, int2*, const Consts<R>*, long long, int, int, SimView<R>, StepIO<R>, int, int,
+                        int);
+  const SeqFn f = (SeqFn)step_seq_fn<R>(s);
+  const unsigned grid = grid_for(s->N, s->tpb);
+  for (int t0 = 0; t0 < n_steps; t0 += kSeqStepsPerLaunch) {
+    const int steps = std::min(kSeqStepsPerLaunch, n_steps - t0);
+    hipLaunchKernelGGL(f, dim3(grid), dim3(3 * kWave), (size_t)s->tile_bytes, st, v.state, actions, v.ctr, c, v.npad,
+                       v.N, v.tpb, v, io, n_slots, t0 % n_slots, steps);
+    HIP_TRY(hipGetLastError());
+  }
   return GPD_OK;
 }
 
@@ -1392,6 +1437,9 @@ int gpd_step_seq(gpd_sim* sim, const float* actions, int n_slots, int n_steps, f
   hipStream_t st = (hipStream_t)stream;
   const size_t slot = (size_t)sim->N * sim->A;
   return by_real(sim, [&](auto r) {
+    if (seq_fused(sim) && n_steps >= 2)
+      return launch_step_seq<decltype(r)>(sim, actions, n_slots, n_steps, obs, reward, terminated, truncated,
+                                          terminal_obs, st);
     for (int t = 0; t < n_steps; ++t) {
       const float* a = actions + (size_t)(t % n_slots) * slot;
       const int rc = launch_step<decltype(r)>(sim, a, obs, reward, terminated, truncated, terminal_obs, st);
@@ -1399,6 +1447,11 @@ int gpd_step_seq(gpd_sim* sim, const float* actions, int n_slots, int n_steps, f
     }
     return (int)GPD_OK;
   });
+}
+
+int gpd_step_seq_plan(const gpd_sim* sim, int n_steps) {
+  if (!sim) return fail(GPD_EINVAL, "gpd_step_seq_plan: NULL sim");
+  return step_seq_launches(sim, n_steps);
 }
 
 int gpd_integrate(gpd_sim* sim, const void* rpm, int n_sub, void* traj, void* stream) {

@@ -30,8 +30,8 @@
 // This header is the umbrella gpd.hip includes; the kernels live in the headers below, one per
 // subsystem, each building on the ones before it.  gpd_step_parts.h holds the phases of a step
 // (substep_block, action load, ring append, history DMA, final readback, hover terms, env
-// reduction, terminal row, reset, tile fill, state20 rows, RPM vectors) that the step, duo, wide,
-// cmd, rollout and het kernels after it are assembled from.
+// reduction, terminal row, reset, tile fill, state20 rows, RPM vectors) that the step, duo, seq,
+// wide, cmd, rollout and het kernels after it are assembled from.
 #pragma once
 #include "gpd_layout.h"
 #include "gpd_narrowphase.h"
@@ -39,6 +39,7 @@
 #include "gpd_step_parts.h"
 #include "gpd_step.h"
 #include "gpd_step_duo.h"
+#include "gpd_step_seq.h"
 #include "gpd_step_wide.h"
 #include "gpd_step_cmd.h"
 #include "gpd_step_rollout.h"

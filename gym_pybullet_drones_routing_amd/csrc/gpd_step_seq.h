@@ -1,0 +1,405 @@
+// gpd_step_seq.h — step_seq_kernel: n_steps consecutive steps of step_kernel_duo<R, ACT, true>
+// (single-drone envs, plain DYN, RPM action types, three waves per block) in ONE launch, for
+// open-loop action sequences (gpd_step_seq, BatchedAviarySim.capture_graph).  The envs of this path
+// do not interact, so a block keeps its drones for the whole sequence, as cmd_rollout_kernel does
+// (gpd_step_rollout.h): the state, the step counters and the constants are loaded once and the
+// state is stored once, the action history lives in the LDS tile, and the kernel boundary with its
+// cold caches is paid once per launch instead of once per step.  Every step still stores what an
+// env.step() returns (observation rows, reward, flags, terminal rows), so after the launch memory
+// holds what n_steps launches of step_kernel_duo would have left, bit for bit.
+// The per-step text of the three waves is step_kernel_duo's (gpd_step_duo.h), written out here
+// because lifting it into helpers changes that kernel's instructions: a fix goes to both.
+// Needs step_kernel_duo's helpers (gpd_step_duo.h).
+#pragma once
+#include "gpd_step_duo.h"
+
+namespace gpd {
+
+// ---------------------------------------------------------------------------------------
+// Arguments: step_kernel_duo's, with actions_p the base of the action slots [n_slots][N][A];
+// step t of the launch reads slot (slot0 + t) % n_slots.  All of them are fixed per launch (the
+// ring head and the step counters live in device memory), so a hipGraph can replay it.
+//   pose wave  the drone, last_clipped_action, the step counter and the ring head in registers;
+//              per step the substeps' pose halves, the final readback, the task hook, the 12 state
+//              columns of the row, reward and flags, the terminal row and the reset of an env that
+//              finishes; the state, the ring mark and {step_counter, head} once, at the end
+//   rate wave  the body rates in registers; per step the substeps' rate halves; it takes the
+//              template's rates (zero) for the lanes the pose wave reset
+//   io wave    the action history: the ring's slots are DMA'd into the tile once, tile slot s
+//              being ring slot s.  Each step writes its action into slot `head` (and into the HBM
+//              ring, a plain store nothing waits for); history column j of a row is then tile slot
+//              (head + 1 + j) mod L, so an element's LDS address advances by one slot per step
+//              and wraps, while its place in the row stays the same.
+// Each wave loads the next step's action row while the current step's substeps run.  A step has
+// nsub hand-off barriers and one final barrier, as in step_kernel_duo; shand is double-buffered
+// by substep parity and the pose wave has read a step's last hand-off before the final barrier,
+// behind which the rate wave writes the next step's first.  sdone / sreset are written in front
+// of a final barrier and read right behind it; the next write is at least one barrier later.
+template <typename R, int ACT>
+__global__ __launch_bounds__(3 * kWave) void step_seq_kernel(R* __restrict__ state_p, const float* __restrict__ actions_p,
+                                                             int2* __restrict__ ctr_p, const Consts<R>* __restrict__ cp,
+                                                             long long npad_p, int n_p, int tpb_p, SimView<R> v,
+                                                             StepIO<R> io, int n_slots, int slot0, int n_steps) {
+  static_assert(!act_is_pid(ACT), "the fused sequence kernel serves the RPM action types");
+  v.state = state_p; v.ctr = ctr_p; v.npad = npad_p; v.N = n_p; v.tpb = tpb_p;
+  constexpr int A = act_width(ACT);
+  constexpr bool kAhead = sizeof(R) == 8;   // the f64 substep order of step_kernel_duo
+  extern __shared__ float4 tile4[];
+  float* tilef = reinterpret_cast<float*>(tile4);
+  __shared__ R shand[2][5][kWave];        // rate_half -> pose_half, by substep parity
+  __shared__ R sw[3][kWave];              // rpy_rates after the last substep
+  __shared__ unsigned long long sdone;    // rows whose terminal observation is wanted (tile rows)
+  __shared__ unsigned long long sreset;   // lanes whose env was reset in this step
+  __shared__ int shead[kWave];            // ring head of every lane's env at entry (io wave)
+  const Consts<R>& c = *cp;
+  const int tid = threadIdx.x & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x) / kWave;   // wave-uniform
+  const long long n0 = (long long)blockIdx.x * v.tpb;
+  const long long n = n0 + tid;
+  const int nact = (int)((v.N - n0) < v.tpb ? (v.N - n0) : v.tpb);
+  const bool active = tid < nact;
+  const long long nn = active ? n : n0;  // inactive lanes compute on the block's first drone, store nothing
+  // the action row of this lane in the slot a step reads; the slot advances and wraps per step
+  const long long slot_stride = (long long)v.N * A;
+  int slot = slot0;
+  auto next_slot = [&]() { slot = slot + 1 == n_slots ? 0 : slot + 1; };
+  float nxt[A];
+
+  if (wave == 2) {
+    // ------------------------------------------------------------ wave 2: history columns
+    const int L = v.ring_len;
+    const int nsub = c.nsub;
+    // the whole ring of the block's drones -> tile, slot s to tile slot s, once per launch
+    {
+      const float* rb = v.ring + ridx(nn, 0, L, A);
+      for (int s = 0; s < L; ++s) {
+        const float* src = rb + (long long)s * (64 * A);
+        if (A == 4) __builtin_amdgcn_global_load_lds((gbl_void_ptr)src, (lds_void_ptr)(tile4 + s * kPad), 16, 0, 0);
+        else __builtin_amdgcn_global_load_lds((gbl_void_ptr)src, (lds_void_ptr)(tilef + s * kPad), 4, 0, 0);
+      }
+    }
+    int hd = v.ctr[nn].y;                         // ring slot receiving the step's action
+    action_load<A>(actions_p + slot * slot_stride, nn, nxt);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the ring is in the tile (before any step writes its slot)
+    shead[tid] = hd;
+    wave_lds_sync();
+    // An element of the block's history columns: row i = g / L, column k = g - i * L, g < nact * L.
+    // Blocks whose elements fit one pass of U per lane (`fits`) form each element's row offset
+    // once and step its tile index; longer histories form both per pass.
+    constexpr int U = 4;                          // elements per lane in flight per pass
+    constexpr int EB = A == 4 ? 16 : 4;           // bytes of a tile element
+    const int total = nact * L;
+    const int NC = A == 4 ? 3 + L : v.W;          // row stride in elements
+    const int c0 = A == 4 ? 3 : 12;               // first history column
+    const float rL = 1.0f / (float)L;             // (g + 0.5) / L: exact row index for g < 2^12
+    const bool fits = total <= U * kWave;
+    const bool wt_rows = (v.wt & 1) != 0;
+    const int span = L * kPad;                    // tile elements of the L slots
+    float* const dst0 = uniform_ptr(io.obs + n0 * v.W);
+    const int nrec = __builtin_amdgcn_readfirstlane(nact * v.W * 4);
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(dst0, 0, nrec, 0x00020000);
+    int off[U], row[U], idx[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      // an element past the end gets an offset past num_records, so the buffer unit drops its store
+      const int g = tid + u * kWave;
+      const bool ok = g < total;
+      const int gg = ok ? g : total - 1;
+      const int i = (int)(((float)gg + 0.5f) * rL), k = gg - i * L;
+      int s = shead[i] + 1 + k;
+      s -= s >= L ? L : 0;
+      s -= s >= L ? L : 0;
+      row[u] = i;
+      off[u] = ok ? (i * NC + c0 + k) * EB : nrec;
+      idx[u] = s * kPad + i;
+    }
+    int tmod = 0;                                 // steps of this launch so far, mod L
+    for (int t = 0; t < n_steps; ++t) {
+      float a[A];
+#pragma unroll
+      for (int j = 0; j < A; ++j) a[j] = nxt[j];
+      next_slot();
+      // the next step's row is in flight while this step's substeps run
+      if (t + 1 < n_steps) action_load<A>(actions_p + slot * slot_stride, nn, nxt);
+      // This wave publishes nothing to the others at the hand-offs, so its barriers there are
+      // plain.  Its work sits behind hand-off 0, where it has a substep of slack (in front of it,
+      // it would be the block's last wave to arrive: step_kernel_duo).
+      asm volatile("s_barrier" ::: "memory");       // hand-off 0
+      if (A == 4) tile4[hd * kPad + tid] = make_float4(a[0], a[1], a[2], a[3]);
+      else tilef[hd * kPad + tid] = a[0];
+      if (active) ring_append<A>(v.ring, n, hd, L, a);   // deque.append
+      wave_lds_sync();
+      float4 v4[U];
+      float v1[U];
+      if (fits) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (A == 4) v4[u] = tile4[idx[u]];
+          else v1[u] = tilef[idx[u]];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (wt_rows) {
+            if (A == 4) store_wt(rsrc, off[u], v4[u]);
+            else store_wt(rsrc, off[u], v1[u]);
+          } else {
+            if (A == 4) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(gpd_v4i, v4[u]), rsrc, off[u], 0, 0);
+            else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v1[u]), rsrc, off[u], 0, 0);
+          }
+        }
+      }
+      // longer histories: one element per lane per pass
+      for (int g = fits ? total : tid; g < total; g += kWave) {
+        const int i = (int)(((float)g + 0.5f) * rL), k = g - i * L;
+        int s = shead[i] + tmod + 1 + k;
+        s -= s >= L ? L : 0;
+        s -= s >= L ? L : 0;
+        const int o = (i * NC + c0 + k) * EB;
+        if (A == 4) {
+          const float4 p = tile4[s * kPad + i];
+          if (wt_rows) store_wt(rsrc, o, p);
+          else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(gpd_v4i, p), rsrc, o, 0, 0);
+        } else {
+          const float p = tilef[s * kPad + i];
+          if (wt_rows) store_wt(rsrc, o, p);
+          else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p), rsrc, o, 0, 0);
+        }
+      }
+      for (int k = 1; k < nsub; ++k) asm volatile("s_barrier" ::: "memory");   // hand-offs 1 .. nsub-1
+      lds_barrier();     // final: sdone published by the pose wave
+      const unsigned long long dr = sdone;
+      if (dr) {          // the history columns of the terminal rows (the tile is unchanged until the next step's write)
+        float* const tdst = io.terminal_obs + n0 * v.W;
+        if (fits) {
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            if (tid + u * kWave < total && ((dr >> row[u]) & 1ull)) {
+              char* const tp = reinterpret_cast<char*>(tdst) + off[u];
+              if (A == 4) *reinterpret_cast<float4*>(tp) = v4[u];
+              else *reinterpret_cast<float*>(tp) = v1[u];
+            }
+          }
+        }
+        for (int g = fits ? total : tid; g < total; g += kWave) {
+          const int i = (int)(((float)g + 0.5f) * rL), k = g - i * L;
+          if ((dr >> i) & 1ull) {
+            int s = shead[i] + tmod + 1 + k;
+            s -= s >= L ? L : 0;
+            s -= s >= L ? L : 0;
+            const int e = i * NC + c0 + k;
+            if (A == 4) reinterpret_cast<float4*>(tdst)[e] = tile4[s * kPad + i];
+            else tdst[e] = tilef[s * kPad + i];
+          }
+        }
+      }
+      // one slot on: the head, every element's tile index, the step count mod L
+      hd = hd + 1 == L ? 0 : hd + 1;
+      tmod = tmod + 1 == L ? 0 : tmod + 1;
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        idx[u] += kPad;
+        idx[u] -= idx[u] >= span ? span : 0;
+      }
+    }
+    return;
+  }
+
+  action_load<A>(actions_p + slot * slot_stride, nn, nxt);
+  const R* st = v.state + tidx(nn, 0, kStateComps);
+
+  if (wave == 1) {
+    // ------------------------------------------------------------ wave 1: body rates
+    R wx = st[10 * 64], wy = st[11 * 64], wz = st[12 * 64];
+    DynK<R> dk = dyn_consts(c);
+    const int nsub = dk.nsub;
+    // the entry loads have landed before the first step: a wait for them left inside the loop
+    // would, from the second step on, wait for the action row just requested
+    asm volatile("" : "+v"(wx), "+v"(wy), "+v"(wz));
+    for (int t = 0; t < n_steps; ++t) {
+      float a[A];
+#pragma unroll
+      for (int j = 0; j < A; ++j) a[j] = nxt[j];
+      next_slot();
+      if (t + 1 < n_steps) action_load<A>(actions_p + slot * slot_stride, nn, nxt);
+      R rpm[4], W[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) rpm[k] = (R)action_to_rpm(dk.hover_f32, a[A == 4 ? k : 0]);
+      rpm_wrench<R, 0>(rpm, dk, c, W);
+      if constexpr (kAhead) {
+        // the recurrence one substep ahead of its weights (step_kernel_duo)
+        rate_recur(wx, wy, wz, W, dk);   // ω_1
+        for (int k = 0; k < nsub - 1; ++k) {
+          R h[5], n2;
+          const R cx = wx, cy = wy, cz = wz;   // ω_{k+1}
+          const bool big = rate_weights(cx, cy, cz, dk, h, n2);
+          rate_weights_big(big, n2, dk, h);
+#pragma unroll
+          for (int j = 0; j < 5; ++j) shand[k & 1][j][tid] = h[j];
+          rate_recur(wx, wy, wz, W, dk);       // ω_{k+2}
+          asm volatile("" : "+v"(wx), "+v"(wy), "+v"(wz));   // (complete in front of the barrier)
+          lds_barrier();   // hand-off k published
+        }
+        {
+          R h[5], n2;
+          const bool big = rate_weights(wx, wy, wz, dk, h, n2);
+          rate_weights_big(big, n2, dk, h);
+#pragma unroll
+          for (int j = 0; j < 5; ++j) shand[(nsub - 1) & 1][j][tid] = h[j];
+          sw[0][tid] = wx; sw[1][tid] = wy; sw[2][tid] = wz;
+          lds_barrier();   // last hand-off and the final rates published
+        }
+      } else {
+        for (int k = 0; k < nsub; ++k) {
+          R h[5];
+          rate_half(wx, wy, wz, W, dk, h);
+#pragma unroll
+          for (int j = 0; j < 5; ++j) shand[k & 1][j][tid] = h[j];
+          if (k == nsub - 1) { sw[0][tid] = wx; sw[1][tid] = wy; sw[2][tid] = wz; }
+          lds_barrier();   // hand-off k published
+        }
+      }
+      lds_barrier();     // final: sreset published by the pose wave
+      // a reset env starts from the template's rates (drone_from_template)
+      if ((sreset >> tid) & 1ull) wx = wy = wz = R(0);
+    }
+    return;
+  }
+
+  // -------------------------------------------------------------- wave 0: pose
+  Drone<R> s;
+  R last[4];
+  load_drone(v, nn, s, last, false);
+  const int2 cv = v.ctr[nn];
+  int sc = cv.x;          // step_counter
+  int head = cv.y;        // ring slot receiving the step's action
+  DynK<R> dk = dyn_consts(c, v.task, io.trunc);
+  const TailK<R> tk = tail_consts(c, v.bound_xy);
+  const int nsub = dk.nsub;
+  // where the lane's results go, formed once (global-address-space pointers, as step_kernel_duo)
+  gpd_global R* st_out = (gpd_global R*)(v.state + tidx(nn, 0, kStateComps));
+  int st_off = (int)(tidx(nn, 0, kStateComps) * sizeof(R));
+  gpd_global float* rew_out = (gpd_global float*)(io.reward + nn);
+  gpd_global uint8_t* term_out = (gpd_global uint8_t*)(io.term + nn);
+  gpd_global uint8_t* trunc_out = (gpd_global uint8_t*)(io.trunc + nn);
+  gpd_global gpd_v2i* ctr_out = (gpd_global gpd_v2i*)(v.ctr + nn);
+  asm volatile("" : "+v"(st_out), "+v"(st_off), "+v"(rew_out), "+v"(term_out), "+v"(trunc_out), "+v"(ctr_out));
+  // the entry loads have landed before the first step: a wait for them left inside the loop would,
+  // from the second step on, wait for the previous step's stores
+  asm volatile("" : "+v"(s.px), "+v"(s.py), "+v"(s.pz), "+v"(s.qx), "+v"(s.qy), "+v"(s.qz), "+v"(s.qw), "+v"(s.vx),
+               "+v"(s.vy), "+v"(s.vz), "+v"(sc), "+v"(head));
+  const R wnone[3] = {R(0), R(0), R(0)};
+  auto hand_off = [&](int k, R h[5]) {
+#pragma unroll
+    for (int j = 0; j < 5; ++j) h[j] = shand[k & 1][j][tid];
+  };
+  for (int t = 0; t < n_steps; ++t) {
+    float a[A];
+#pragma unroll
+    for (int j = 0; j < A; ++j) a[j] = nxt[j];
+    next_slot();
+    if (t + 1 < n_steps) action_load<A>(actions_p + slot * slot_stride, nn, nxt);
+    R fz;
+    {
+      R rpm[4], W[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) rpm[k] = (R)action_to_rpm(dk.hover_f32, a[A == 4 ? k : 0]);
+      rpm_wrench<R, 0>(rpm, dk, c, W);
+      fz = W[0];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) last[k] = rpm[k];   // self.last_clipped_action = clipped_action  :372
+    }
+    if (nsub > 1) {
+      lds_barrier();   // hand-off 0
+      R h[5];
+      hand_off(0, h);
+      pose_half<R, false, true>(s, fz, h, wnone, dk);
+      for (int k = 1; k < nsub - 1; ++k) {
+        lds_barrier();   // hand-off k
+        hand_off(k, h);
+        pose_half<R, false, false>(s, fz, h, wnone, dk);
+      }
+    }
+    {
+      lds_barrier();   // last hand-off + final rates
+      R h[5];
+      hand_off(nsub - 1, h);
+      s.wx = sw[0][tid]; s.wy = sw[1][tid]; s.wz = sw[2][tid];
+      const R w[3] = {s.wx, s.wy, s.wz};
+      if (nsub > 1) pose_half<R, true, false>(s, fz, h, w, dk);
+      else pose_half<R, true, true>(s, fz, h, w, dk);
+    }
+    // final readback (:374) -> obs / reward / done
+    R qn[4], Rm[9];
+    if constexpr (kAhead) readback_fused_rare(s.qx, s.qy, s.qz, s.qw, qn, Rm);
+    else readback_fused(s.qx, s.qy, s.qz, s.qw, qn, Rm);
+    AttitudeArgs<R> att = attitude_args(qn);
+    bool tilted, up_unused;   // |roll| or |pitch| > 0.4, decided exactly near the limit (attitude_decide)
+    attitude_decide<R, true, false>(s.qx, s.qy, s.qz, s.qw, att, tilted, up_unused);
+    float roll, pitch, yaw;
+    obs_euler_f32(qn, att, roll, pitch, yaw);
+    float reward = -1.0f;
+    bool term = false, trunc = false;
+    if (v.task != TASK_NONE) {
+      const R tx = tk.tg[0] - s.px, ty = tk.tg[1] - s.py, tz = tk.tg[2] - s.pz;
+      const R d2 = hover_d2(tx, ty, tz);
+      R r = R(2) - d2 * d2;
+      r = r > R(0) ? r : R(0);
+      const bool oob = g_abs(s.px) > tk.bound_xy || g_abs(s.py) > tk.bound_xy || s.pz > R(2) || tilted;
+      reward = (float)r;
+      // np.linalg.norm(...) < .0001 (HoverAviary.py:92) with the root taken only inside the band
+      // where it decides (step_kernel_duo)
+      term = d2 < R(0.99e-8);
+      const bool band = !(d2 < R(0.99e-8)) && !(d2 > R(1.01e-8));   // a NaN goes the root's way, too
+      if (GPD_RARE(__ballot(band) != 0ull)) term = g_sqrt(d2) < R(1e-4);
+      trunc = oob || sc >= v.trunc_sc;
+    }
+    const bool done = term || trunc;
+    const bool do_reset = done && v.autoreset;
+    float row12[12] = {(float)s.px, (float)s.py, (float)s.pz, roll, pitch, yaw,
+                       (float)s.vx, (float)s.vy, (float)s.vz, (float)s.ax, (float)s.ay, (float)s.az};
+    if (do_reset) {
+      if (active && io.terminal_obs != nullptr) row12_store<A>(io.terminal_obs + n * v.W, row12);
+      reset_to_template(tk.ini, s, last, row12);
+    }
+    const unsigned long long done_rows = __ballot(do_reset && active && io.terminal_obs != nullptr);
+    const unsigned long long reset_rows = __ballot(do_reset);
+    // the row's 12 state columns straight from registers; the io wave writes the rest
+    if (active) {
+      if (A == 4) {
+        const float4 r0 = make_float4(row12[0], row12[1], row12[2], row12[3]);
+        const float4 r1 = make_float4(row12[4], row12[5], row12[6], row12[7]);
+        const float4 r2 = make_float4(row12[8], row12[9], row12[10], row12[11]);
+        if (v.wt & 1) {
+          const __amdgpu_buffer_rsrc_t r =
+              __builtin_amdgcn_make_buffer_rsrc(io.obs + n0 * v.W, 0, nact * v.W * 4, 0x00020000);
+          const int o = tid * v.W * 4;
+          store_wt(r, o, r0); store_wt(r, o + 16, r1); store_wt(r, o + 32, r2);
+        } else {
+          float4* o4 = reinterpret_cast<float4*>(io.obs + n * v.W);
+          o4[0] = r0; o4[1] = r1; o4[2] = r2;
+        }
+      } else {
+        float* orow = io.obs + n * v.W;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) orow[k] = row12[k];
+      }
+    }
+    if (tid == 0) { sdone = done_rows; sreset = reset_rows; }
+    lds_barrier();   // final: sdone / sreset published
+    // every step leaves its reward and flags; the same lane writes the same address each step, so
+    // the last step's values stay.  Nothing waits for these stores before the launch ends.
+    if (active) {
+      *rew_out = reward;
+      *term_out = (uint8_t)(term ? 1 : 0);
+      *trunc_out = (uint8_t)(trunc ? 1 : 0);
+    }
+    sc = do_reset ? 0 : sc + nsub;
+    head = head + 1 == v.ring_len ? 0 : head + 1;
+  }
+  if (!active) return;
+  store_drone_step_at<R, kAuxWt>(v, st_out, st_off, s, last);
+  mark_last_in_ring_single(v, n);
+  *ctr_out = gpd_v2i{sc, head};
+}
+
+}  // namespace gpd

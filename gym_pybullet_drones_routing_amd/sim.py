@@ -140,6 +140,28 @@ def pack_layout(n_envs, drones_per_env, obs_width, align=256):
     return out
 
 
+def seq_segments(data_ptrs, slot_bytes):
+    """Split a sequence of action tensors, given by their addresses, into the longest runs one
+    ``gpd_step_seq`` call can express: ``[(base, n_slots, n_steps), ...]`` with tensor ``k`` of a
+    run at ``base + (k % n_slots) * slot_bytes``.  A run grows while the tensors follow each other
+    in memory; the first return to ``base`` fixes ``n_slots``, and the run then lasts as long as
+    the tensors keep cycling through those slots.  Unrelated tensors are runs of one step."""
+    ptrs = [int(p) for p in data_ptrs]
+    out, i = [], 0
+    while i < len(ptrs):
+        base, n_slots, k = ptrs[i], None, 1
+        while i + k < len(ptrs):
+            p = ptrs[i + k]
+            if n_slots is None and p == base:
+                n_slots = k
+            if p != base + (k % n_slots if n_slots else k) * slot_bytes:
+                break
+            k += 1
+        out.append((base, n_slots or k, k))
+        i += k
+    return out
+
+
 def env_param_rows(params, n_envs, env_params=None):
     """``gpd_env_params`` rows [E, 11] float64 (column order ``_lib.ENV_PARAM_NAMES``): the values of
     ``params`` (a ``_lib.DroneParams``) for every env, with the columns named in the dict
@@ -556,31 +578,45 @@ class BatchedAviarySim:
                 and a.is_contiguous() and a.numel() % (self.n_drones * self.act_width) == 0):
             raise ValueError("step_seq needs contiguous float32 action slots [P, E, D, A] on the sim's device")
         P = a.numel() // (self.n_drones * self.act_width)
+        self._step_seq_at(a.data_ptr(), P, n_steps, terminal_obs)
+        return self.obs, self.reward, self.terminated, self.truncated
+
+    def _step_seq_at(self, base, n_slots, n_steps, terminal_obs):
         tptr = self._tobs_ptr if terminal_obs else None
         with torch.cuda.device(self.device):
-            rc = self._lib.gpd_step_seq(self._h, ctypes.c_void_p(a.data_ptr()), int(P), int(n_steps), *self._out_ptrs,
+            rc = self._lib.gpd_step_seq(self._h, ctypes.c_void_p(base), int(n_slots), int(n_steps), *self._out_ptrs,
                                         tptr, _stream(self.device))
         if rc != 0:
             self._step_failed("gpd_step_seq", rc)
-        return self.obs, self.reward, self.terminated, self.truncated
 
     def capture_graph(self, actions_seq, terminal_obs=True):
-        """Record ``len(actions_seq)`` consecutive :meth:`step` launches into one HIP graph
+        """Record ``len(actions_seq)`` consecutive :meth:`step` calls into one HIP graph
         (``torch.cuda.CUDAGraph``).  Each ``replay()`` advances every env by that many steps,
-        reading the given action tensors (refill them in place between replays).  gpd_step is
-        a fixed-argument launch - the ring head and step counters live in device memory - so
-        one recorded sequence stays valid for any number of replays.  Capture records only;
-        the sim does not advance until the first replay."""
+        reading the given action tensors (refill them in place between replays).  The launches
+        have fixed arguments - the ring head and step counters live in device memory - so one
+        recorded sequence stays valid for any number of replays.  Capture records only; the sim
+        does not advance until the first replay.
+
+        Tensors that follow each other in memory, or cycle through such a run of slots
+        (``[pool[k % P] for k in range(K)]``, one tensor repeated), are recorded as one
+        ``gpd_step_seq`` call (:func:`seq_segments`), which the sims of the three-wave step kernel
+        run as one fused launch per 256 steps; unrelated tensors are one launch each."""
         seq = []
         for a in actions_seq:
             if not (isinstance(a, torch.Tensor) and a.device == self.device and a.dtype == torch.float32
                     and a.is_contiguous() and a.numel() == self.n_drones * self.act_width):
                 raise ValueError("capture_graph needs contiguous float32 action tensors on the sim's device")
             seq.append(a)
+        segments = seq_segments([a.data_ptr() for a in seq], self.n_drones * self.act_width * 4)
         g = torch.cuda.CUDAGraph()
         with graph_capture(g, self.device):
-            for a in seq:
-                self.step(a, terminal_obs=terminal_obs)
+            k = 0
+            for base, n_slots, n_steps in segments:
+                if n_steps == 1:
+                    self.step(seq[k], terminal_obs=terminal_obs)
+                else:
+                    self._step_seq_at(base, n_slots, n_steps, terminal_obs)
+                k += n_steps
         return g
 
     # ------------------------------------------------------------------ command step (CtrlAviary / VelocityAviary)

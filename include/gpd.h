@@ -287,10 +287,19 @@ int gpd_step(gpd_sim* sim, const float* actions, float* obs, float* reward,
 /* n_steps consecutive gpd_step calls issued from native code (open-loop action sequences:
  * playback, benchmarks): step t reads action slot t % n_slots of actions
  * [n_slots][E][D][act_width]; every step writes the same output buffers (as n_steps gpd_step
- * calls would), so they hold the last step's outputs.  One kernel launch per step, no host
- * round trip in between. */
+ * calls would), so they hold the last step's outputs.  No host round trip in between.
+ * A sim whose step is the three-wave kernel (single-drone envs, plain DYN, RPM action types, up to
+ * 4096 envs; not het) runs n_steps >= 2 as one fused launch per 256 steps: a block keeps its
+ * drones, counters and action history on chip between the steps, every step still stores its
+ * outputs, and the result is bit-identical to n_steps gpd_step calls.  Every other sim gets one
+ * kernel launch per step.  The launches have fixed arguments, so the call can be captured in a
+ * graph and replayed. */
 int gpd_step_seq(gpd_sim* sim, const float* actions, int n_slots, int n_steps, float* obs, float* reward,
                  uint8_t* terminated, uint8_t* truncated, float* terminal_obs, void* stream);
+
+/* The number of kernel launches gpd_step_seq(sim, ..., n_steps, ...) would issue (0 for
+ * n_steps <= 0); GPD_EINVAL for a NULL sim.  A pure function of the sim: no device call. */
+int gpd_step_seq_plan(const gpd_sim* sim, int n_steps);
 
 /* Raw DYN integrator: n_sub substeps, row t of rpm [n_sub][N][4] (real) drives substep t of
  * every drone; each substep is followed by the readback (PYB_STEPS_PER_CTRL = 1 cadence).
