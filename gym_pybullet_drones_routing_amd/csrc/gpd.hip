@@ -15,7 +15,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -56,6 +58,8 @@ struct gpd_sim {
   void* d_target = nullptr;
   void* d_consts = nullptr;       // Consts<real> in device memory
   int tile_bytes = 0;             // dynamic LDS of the step kernel
+  int seq_lds = 0;                // dynamic LDS of step_seq_kernel (tile + the rate chains' hand-off buffers);
+                                  // 0: the sim is not seq_fused (prepare_step_kernel)
   int wt = 0;                     // SimView::wt (write-through store policy)
   int nc_magic = 0;               // SimView::nc_magic
   bool duo = false;               // step launches step_kernel_duo (two or three waves per block)
@@ -334,9 +338,12 @@ const void* step_kernel_fn(const gpd_sim* s) {
 // step_kernel_duo<R, ACT, true>, one launch per kSeqStepsPerLaunch steps (gpd_cmd_rollout's default).
 // f64 only: hipcc contracts the f32 instantiation's multiply-adds differently from the per-step
 // kernel's (observations differ in last bits after 40 steps), so f32 sims keep the per-step loop
-// and the f32 kernel is not built.
+// and the f32 kernel is not built.  The kernel's hand-off buffers grow with the block's drones and
+// the substeps (seq_lds_bytes); a sim whose buffers do not fit the workgroup's LDS beside the tile
+// keeps the per-step loop as well (prepare_step_kernel decides: seq_lds).
 constexpr int kSeqStepsPerLaunch = 256;
-inline bool seq_fused(const gpd_sim* s) { return s->duo && s->step_waves == 3 && s->prec == GPD_F64; }
+inline bool seq_kind(const gpd_sim* s) { return s->duo && s->step_waves == 3 && s->prec == GPD_F64; }
+inline bool seq_fused(const gpd_sim* s) { return seq_kind(s) && s->seq_lds > 0; }
 template <typename R>
 const void* step_seq_fn(const gpd_sim* s) {
   if constexpr (sizeof(R) == 8)
@@ -361,6 +368,21 @@ size_t runtime_step_lds(int act, bool multi) {
     return kLdsBytes;
   }
   return fa.sharedSizeBytes;
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize belongs to the kernel, not to a sim: it is only ever
+// raised, so a later sim that needs less does not lower it under a live sim that needs more
+inline hipError_t raise_dynamic_lds(const void* f, int bytes) {
+  static std::mutex mu;
+  static std::map<std::pair<int, const void*>, int> set_to;   // by device and kernel
+  int dev = 0;
+  if (const hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+  std::lock_guard<std::mutex> lock(mu);
+  int& cur = set_to[{dev, f}];
+  if (bytes <= cur) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) cur = bytes;
+  return e;
 }
 
 // the LDS budget and dynamic-LDS attribute of the step kernel the sim launches (again when a reset
@@ -388,10 +410,18 @@ int prepare_step_kernel(gpd_sim* s) {
     return fail(GPD_EUNSUPPORTED, "gpd_create: ctrl_freq too high for drone <-> drone contact (observation tile + "
                                   "the step kernel's LDS exceed 160 KiB; GPD_F_NO_DRONE_CONTACT lifts the limit)");
   // the observation tile can exceed the 64 KiB default dynamic-LDS limit for long histories
-  if (s->tile_bytes > 65536) {
-    HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, s->tile_bytes));
-    if (seq_fused(s))   // gpd_step_seq's fused kernel keeps its action history in the same tile
-      HIP_TRY(hipFuncSetAttribute(step_seq_fn<R>(s), hipFuncAttributeMaxDynamicSharedMemorySize, s->tile_bytes));
+  if (s->tile_bytes > 65536) HIP_TRY(raise_dynamic_lds(f, s->tile_bytes));
+  // gpd_step_seq's fused kernel keeps its action history in the same tile, with the rate chains'
+  // hand-off buffers behind it
+  s->seq_lds = 0;
+  if (seq_kind(s)) {
+    const void* fs = step_seq_fn<R>(s);
+    const size_t need = seq_lds_bytes(s->tile_bytes, s->nsub, s->tpb, sizeof(R));
+    HIP_TRY(hipFuncGetAttributes(&fa, fs));
+    if (fa.sharedSizeBytes + need <= kLdsBytes) {
+      s->seq_lds = (int)need;
+      if (need > 65536) HIP_TRY(raise_dynamic_lds(fs, (int)need));
+    }
   }
   return GPD_OK;
 }
@@ -513,13 +543,13 @@ int launch_step_seq(gpd_sim* s, const float* actions, int n_slots, int n_steps, 
   const SimView<R> v = make_view<R>(s);
   const Consts<R>* c = (const Consts<R>*)s->d_consts;
   typedef void (*SeqFn)(R*, const float*, int2*, const Consts<R>*, long long, int, int, SimView<R>, StepIO<R>, int, int,
-                        int);
+                        int, int);
   const SeqFn f = (SeqFn)step_seq_fn<R>(s);
   const unsigned grid = grid_for(s->N, s->tpb);
   for (int t0 = 0; t0 < n_steps; t0 += kSeqStepsPerLaunch) {
     const int steps = std::min(kSeqStepsPerLaunch, n_steps - t0);
-    hipLaunchKernelGGL(f, dim3(grid), dim3(3 * kWave), (size_t)s->tile_bytes, st, v.state, actions, v.ctr, c, v.npad,
-                       v.N, v.tpb, v, io, n_slots, t0 % n_slots, steps);
+    hipLaunchKernelGGL(f, dim3(grid), dim3(4 * kWave), (size_t)s->seq_lds, st, v.state, actions, v.ctr, c, v.npad,
+                       v.N, v.tpb, v, io, n_slots, t0 % n_slots, steps, seq_hand_off_at(s->tile_bytes));
     HIP_TRY(hipGetLastError());
   }
   return GPD_OK;

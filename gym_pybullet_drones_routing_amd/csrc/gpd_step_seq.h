@@ -1,5 +1,5 @@
 // gpd_step_seq.h — step_seq_kernel: n_steps consecutive steps of step_kernel_duo<R, ACT, true>
-// (single-drone envs, plain DYN, RPM action types, three waves per block) in ONE launch, for
+// (single-drone envs, plain DYN, RPM action types; four waves per block here) in ONE launch, for
 // open-loop action sequences (gpd_step_seq, BatchedAviarySim.capture_graph).  The envs of this path
 // do not interact, so a block keeps its drones for the whole sequence, as cmd_rollout_kernel does
 // (gpd_step_rollout.h): the state, the step counters and the constants are loaded once and the
@@ -7,8 +7,8 @@
 // cold caches is paid once per launch instead of once per step.  Every step still stores what an
 // env.step() returns (observation rows, reward, flags, terminal rows), so after the launch memory
 // holds what n_steps launches of step_kernel_duo would have left, bit for bit.
-// The per-step text of the three waves is step_kernel_duo's (gpd_step_duo.h), written out here
-// because lifting it into helpers changes that kernel's instructions: a fix goes to both.
+// The arithmetic of the waves is step_kernel_duo's (gpd_step_duo.h), written out here because
+// lifting it into helpers changes that kernel's instructions: a fix goes to both.
 // Needs step_kernel_duo's helpers (gpd_step_duo.h).
 #pragma once
 #include "gpd_step_duo.h"
@@ -23,34 +23,99 @@ namespace gpd {
 //              per step the substeps' pose halves, the final readback, the task hook, the 12 state
 //              columns of the row, reward and flags, the terminal row and the reset of an env that
 //              finishes; the state, the ring mark and {step_counter, head} once, at the end
-//   rate wave  the body rates in registers; per step the substeps' rate halves; it takes the
-//              template's rates (zero) for the lanes the pose wave reset
-//   io wave    the action history: the ring's slots are DMA'd into the tile once, tile slot s
+//   rate waves the body rates in registers; the substeps' rate halves of the NEXT step, from the
+//              true rates (chain a) and from the template's zero rates (chain b), see below
+//   io wave   the action history: the ring's slots are DMA'd into the tile once, tile slot s
 //              being ring slot s.  Each step writes its action into slot `head` (and into the HBM
 //              ring, a plain store nothing waits for); history column j of a row is then tile slot
 //              (head + 1 + j) mod L, so an element's LDS address advances by one slot per step
 //              and wraps, while its place in the row stays the same.
-// Each wave loads the next step's action row while the current step's substeps run.  A step has
-// nsub hand-off barriers and one final barrier, as in step_kernel_duo; shand is double-buffered
-// by substep parity and the pose wave has read a step's last hand-off before the final barrier,
-// behind which the rate wave writes the next step's first.  sdone / sreset are written in front
-// of a final barrier and read right behind it; the next write is at least one barrier later.
+//
+// The rate chain a step ahead.  The body-rate chain of a step needs the step's action and the
+// rates at its start, nothing of the pose (gpd_device.h, above rate_recur), and an open-loop
+// sequence has every action in memory.  So while the pose wave runs step t, the rate work of step
+// t+1 is done in full under both outcomes of step t's reset decision, by two rate waves:
+//   chain a (wave 1)  from the true rates at the end of step t.  Those are known behind the barrier
+//                     of step t-1: the lanes reset in step t-1 (sreset) ran step t on chain b's
+//                     rates, the others on chain a's own
+//   chain b (wave 3)  from the template's rates, zero (drone_from_template): a lane reset in step t
+// Each writes the substeps' weights h[5] and its end rates to the hand-off buffer, which lies in
+// dynamic LDS behind the tile: [step parity][chain][lane < tpb][seq_rows(nsub)] reals.  Behind the
+// barrier of step t the pose wave holds sreset(t) in a register, reads step t+1's rows per lane
+// from chain b where the lane was reset and from chain a otherwise, and runs its nsub pose halves
+// with no barrier between them.
+// ONE barrier per step for all four waves.  In front of the barrier of step t the pose wave
+// publishes sdone / sreset of step t and the rate waves the rows of step t+1; behind it the rate
+// waves write the rows of step t+2 where step t's were, which the pose wave has read.  sdone /
+// sreset are double-buffered by step parity: the readers of step t's (io wave, chain a) read them
+// between the barriers of steps t and t+1, the pose wave writes step t+1's in the same interval
+// and step t+2's behind the next barrier.  The first step of a launch has chain a alone, computed
+// from the stored rates in front of an entry barrier; in the last step the rate waves compute
+// nothing.  Every wave meets n_steps + 1 barriers.
+// Each wave loads its next action row while it works on the current one.
+
+// rows of a lane in one chain's hand-off buffer: 5 weights per substep and the 3 end rates, made
+// odd so that the lanes' rows start in different LDS banks
+__host__ __device__ inline int seq_rows(int nsub) { return (5 * nsub + 3) | 1; }
+// the hand-off buffers' place behind the tile, and the kernel's dynamic LDS
+__host__ __device__ inline int seq_hand_off_at(int tile_bytes) { return (tile_bytes + 15) & ~15; }
+inline size_t seq_lds_bytes(int tile_bytes, int nsub, int tpb, size_t real_bytes) {
+  return (size_t)seq_hand_off_at(tile_bytes) + (size_t)2 * 2 * seq_rows(nsub) * tpb * real_bytes;
+}
+
+// The last pose half of a step of nsub > 1 substeps: pose_half<R, true, false> (gpd_device.h)
+// with the x row of the world-frame ang_v spelled out.  Left to hipcc, this kernel (no hand-off
+// barrier in front of the call) takes Rm0 wx as the plain product of (Rm0 wx + Rm1 wy) and fuses
+// Rm1 wy, where step_kernel_duo takes Rm1 wy and fuses Rm0 wx: one ulp apart in ang_v x (measured:
+// every other state column had step_kernel_duo's bits).  The y and z rows and everything else
+// contract as there.  The other lines repeat pose_half's and must stay in step with them.
+template <typename R>
+__device__ __forceinline__ R seq_angv_x(const R Rm[9], const R w[3]) {
+#pragma clang fp contract(off)
+  if constexpr (sizeof(R) == 8) return __builtin_fma(Rm[2], w[2], __builtin_fma(Rm[0], w[0], Rm[1] * w[1]));
+  else return (Rm[0] * w[0] + Rm[1] * w[1]) + Rm[2] * w[2];
+}
+template <typename R>
+__device__ __forceinline__ void seq_pose_half_last(Drone<R>& s, R fz, const R h[5], const R w[3], const DynK<R>& k) {
+  R q0[4] = {s.qx, s.qy, s.qz, s.qw};
+  R d = q0[0] * q0[0] + q0[1] * q0[1] + q0[2] * q0[2] + q0[3] * q0[3];
+  R inv, Rm[9];
+  readback_unit<R, true, false>(q0[0], q0[1], q0[2], q0[3], d, inv, Rm);
+  R Fx = Rm[2] * fz, Fy = Rm[5] * fz, Fz = Rm[8] * fz;
+  Fz = Fz - k.gravity;
+  s.vx = s.vx + k.dt * (Fx * k.inv_m);
+  s.vy = s.vy + k.dt * (Fy * k.inv_m);
+  s.vz = s.vz + k.dt * (Fz * k.inv_m);
+  s.px = s.px + k.dt * s.vx;
+  s.py = s.py + k.dt * s.vy;
+  s.pz = s.pz + k.dt * s.vz;
+  const R shi = h[1] * inv;
+  const R P = h[2] * shi, Q = h[3] * shi, Rr = h[4] * shi;
+  const R C = h[0] * inv;
+  const R x = q0[0], y = q0[1], z = q0[2], ww = q0[3];
+  s.qx = ((C * x + Rr * y) - Q * z) + P * ww;
+  s.qy = ((-Rr * x + C * y) + P * z) + Q * ww;
+  s.qz = ((Q * x - P * y) + C * z) + Rr * ww;
+  s.qw = ((-P * x - Q * y) - Rr * z) + C * ww;
+  s.ax = seq_angv_x(Rm, w);
+  s.ay = (Rm[3] * w[0] + Rm[4] * w[1]) + Rm[5] * w[2];
+  s.az = (Rm[6] * w[0] + Rm[7] * w[1]) + Rm[8] * w[2];
+}
+
 template <typename R, int ACT>
-__global__ __launch_bounds__(3 * kWave) void step_seq_kernel(R* __restrict__ state_p, const float* __restrict__ actions_p,
+__global__ __launch_bounds__(4 * kWave) void step_seq_kernel(R* __restrict__ state_p, const float* __restrict__ actions_p,
                                                              int2* __restrict__ ctr_p, const Consts<R>* __restrict__ cp,
                                                              long long npad_p, int n_p, int tpb_p, SimView<R> v,
-                                                             StepIO<R> io, int n_slots, int slot0, int n_steps) {
+                                                             StepIO<R> io, int n_slots, int slot0, int n_steps,
+                                                             int hand_off_at) {
   static_assert(!act_is_pid(ACT), "the fused sequence kernel serves the RPM action types");
   v.state = state_p; v.ctr = ctr_p; v.npad = npad_p; v.N = n_p; v.tpb = tpb_p;
   constexpr int A = act_width(ACT);
-  constexpr bool kAhead = sizeof(R) == 8;   // the f64 substep order of step_kernel_duo
   extern __shared__ float4 tile4[];
   float* tilef = reinterpret_cast<float*>(tile4);
-  __shared__ R shand[2][5][kWave];        // rate_half -> pose_half, by substep parity
-  __shared__ R sw[3][kWave];              // rpy_rates after the last substep
-  __shared__ unsigned long long sdone;    // rows whose terminal observation is wanted (tile rows)
-  __shared__ unsigned long long sreset;   // lanes whose env was reset in this step
-  __shared__ int shead[kWave];            // ring head of every lane's env at entry (io wave)
+  __shared__ unsigned long long sdone[2];    // rows whose terminal observation is wanted (tile rows), by step parity
+  __shared__ unsigned long long sreset[2];   // lanes whose env was reset in the step, by step parity
+  __shared__ int shead[kWave];               // ring head of every lane's env at entry (io wave)
   const Consts<R>& c = *cp;
   const int tid = threadIdx.x & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x) / kWave;   // wave-uniform
@@ -64,11 +129,18 @@ __global__ __launch_bounds__(3 * kWave) void step_seq_kernel(R* __restrict__ sta
   int slot = slot0;
   auto next_slot = [&]() { slot = slot + 1 == n_slots ? 0 : slot + 1; };
   float nxt[A];
+  // the hand-off buffers [parity][chain][lane][rows]; the lanes past the block's drones compute
+  // on its first drone (nn), read lane 0's rows and write none
+  R* const hbuf = reinterpret_cast<R*>(reinterpret_cast<char*>(tile4) + hand_off_at);
+  const int rows = seq_rows(c.nsub);
+  const int cstride = v.tpb * rows;        // chain a -> chain b
+  const int pstride = 2 * cstride;         // even step -> odd step
+  const bool own = tid < v.tpb;
+  const int lrow = (own ? tid : 0) * rows;
 
   if (wave == 2) {
     // ------------------------------------------------------------ wave 2: history columns
     const int L = v.ring_len;
-    const int nsub = c.nsub;
     // the whole ring of the block's drones -> tile, slot s to tile slot s, once per launch
     {
       const float* rb = v.ring + ridx(nn, 0, L, A);
@@ -114,6 +186,7 @@ __global__ __launch_bounds__(3 * kWave) void step_seq_kernel(R* __restrict__ sta
       idx[u] = s * kPad + i;
     }
     int tmod = 0;                                 // steps of this launch so far, mod L
+    asm volatile("s_barrier" ::: "memory");       // entry (this wave publishes nothing to the others there)
     for (int t = 0; t < n_steps; ++t) {
       float a[A];
 #pragma unroll
@@ -121,10 +194,6 @@ __global__ __launch_bounds__(3 * kWave) void step_seq_kernel(R* __restrict__ sta
       next_slot();
       // the next step's row is in flight while this step's substeps run
       if (t + 1 < n_steps) action_load<A>(actions_p + slot * slot_stride, nn, nxt);
-      // This wave publishes nothing to the others at the hand-offs, so its barriers there are
-      // plain.  Its work sits behind hand-off 0, where it has a substep of slack (in front of it,
-      // it would be the block's last wave to arrive: step_kernel_duo).
-      asm volatile("s_barrier" ::: "memory");       // hand-off 0
       if (A == 4) tile4[hd * kPad + tid] = make_float4(a[0], a[1], a[2], a[3]);
       else tilef[hd * kPad + tid] = a[0];
       if (active) ring_append<A>(v.ring, n, hd, L, a);   // deque.append
@@ -165,9 +234,8 @@ __global__ __launch_bounds__(3 * kWave) void step_seq_kernel(R* __restrict__ sta
           else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p), rsrc, o, 0, 0);
         }
       }
-      for (int k = 1; k < nsub; ++k) asm volatile("s_barrier" ::: "memory");   // hand-offs 1 .. nsub-1
-      lds_barrier();     // final: sdone published by the pose wave
-      const unsigned long long dr = sdone;
+      lds_barrier();     // the step's barrier: sdone published by the pose wave
+      const unsigned long long dr = sdone[t & 1];
       if (dr) {          // the history columns of the terminal rows (the tile is unchanged until the next step's write)
         float* const tdst = io.terminal_obs + n0 * v.W;
         if (fits) {
@@ -204,68 +272,84 @@ __global__ __launch_bounds__(3 * kWave) void step_seq_kernel(R* __restrict__ sta
     return;
   }
 
-  action_load<A>(actions_p + slot * slot_stride, nn, nxt);
   const R* st = v.state + tidx(nn, 0, kStateComps);
 
-  if (wave == 1) {
-    // ------------------------------------------------------------ wave 1: body rates
-    R wx = st[10 * 64], wy = st[11 * 64], wz = st[12 * 64];
+  if (wave != 0) {
+    // ------------------------------------------------------------ waves 1 and 3: body rates
+    const bool from_zero = wave == 3;      // chain b
+    R* const hw = hbuf + (from_zero ? cstride : 0) + lrow;
+    // chain a starts with step 0, from the stored rates; chain b with step 1, from zero
+    if (from_zero) next_slot();
+    if (!from_zero || n_steps > 1) action_load<A>(actions_p + slot * slot_stride, nn, nxt);
+    R wx = R(0), wy = R(0), wz = R(0);
+    if (!from_zero) { wx = st[10 * 64]; wy = st[11 * 64]; wz = st[12 * 64]; }
     DynK<R> dk = dyn_consts(c);
     const int nsub = dk.nsub;
     // the entry loads have landed before the first step: a wait for them left inside the loop
     // would, from the second step on, wait for the action row just requested
     asm volatile("" : "+v"(wx), "+v"(wy), "+v"(wz));
-    for (int t = 0; t < n_steps; ++t) {
+    // the rate work of step u, whose action row is in nxt: the substeps' weights and the end
+    // rates into `out`.  The recurrence is written one substep ahead of its weights as in
+    // step_kernel_duo.  There it hid the recurrence behind a hand-off barrier; here no barrier is
+    // left to hide it behind, and the order is kept because it is the text whose contractions give
+    // step_kernel_duo's bits (the tests compare them).  Per lane the operations are the same.
+    auto chain = [&](int u, R* out) {
       float a[A];
 #pragma unroll
       for (int j = 0; j < A; ++j) a[j] = nxt[j];
       next_slot();
-      if (t + 1 < n_steps) action_load<A>(actions_p + slot * slot_stride, nn, nxt);
+      if (u + 1 < n_steps) action_load<A>(actions_p + slot * slot_stride, nn, nxt);
       R rpm[4], W[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) rpm[k] = (R)action_to_rpm(dk.hover_f32, a[A == 4 ? k : 0]);
       rpm_wrench<R, 0>(rpm, dk, c, W);
-      if constexpr (kAhead) {
-        // the recurrence one substep ahead of its weights (step_kernel_duo)
-        rate_recur(wx, wy, wz, W, dk);   // ω_1
-        for (int k = 0; k < nsub - 1; ++k) {
-          R h[5], n2;
-          const R cx = wx, cy = wy, cz = wz;   // ω_{k+1}
-          const bool big = rate_weights(cx, cy, cz, dk, h, n2);
-          rate_weights_big(big, n2, dk, h);
+      rate_recur(wx, wy, wz, W, dk);   // ω_1
+      for (int k = 0; k < nsub - 1; ++k) {
+        R h[5], n2;
+        const R cx = wx, cy = wy, cz = wz;   // ω_{k+1}
+        const bool big = rate_weights(cx, cy, cz, dk, h, n2);
+        rate_weights_big(big, n2, dk, h);
+        if (own) {
 #pragma unroll
-          for (int j = 0; j < 5; ++j) shand[k & 1][j][tid] = h[j];
-          rate_recur(wx, wy, wz, W, dk);       // ω_{k+2}
-          asm volatile("" : "+v"(wx), "+v"(wy), "+v"(wz));   // (complete in front of the barrier)
-          lds_barrier();   // hand-off k published
+          for (int j = 0; j < 5; ++j) out[5 * k + j] = h[j];
         }
-        {
-          R h[5], n2;
-          const bool big = rate_weights(wx, wy, wz, dk, h, n2);
-          rate_weights_big(big, n2, dk, h);
+        rate_recur(wx, wy, wz, W, dk);       // ω_{k+2}
+      }
+      {
+        R h[5], n2;
+        const bool big = rate_weights(wx, wy, wz, dk, h, n2);
+        rate_weights_big(big, n2, dk, h);
+        if (own) {
+          R* const o = out + 5 * (nsub - 1);
 #pragma unroll
-          for (int j = 0; j < 5; ++j) shand[(nsub - 1) & 1][j][tid] = h[j];
-          sw[0][tid] = wx; sw[1][tid] = wy; sw[2][tid] = wz;
-          lds_barrier();   // last hand-off and the final rates published
-        }
-      } else {
-        for (int k = 0; k < nsub; ++k) {
-          R h[5];
-          rate_half(wx, wy, wz, W, dk, h);
-#pragma unroll
-          for (int j = 0; j < 5; ++j) shand[k & 1][j][tid] = h[j];
-          if (k == nsub - 1) { sw[0][tid] = wx; sw[1][tid] = wy; sw[2][tid] = wz; }
-          lds_barrier();   // hand-off k published
+          for (int j = 0; j < 5; ++j) o[j] = h[j];
+          o[5] = wx; o[6] = wy; o[7] = wz;
         }
       }
-      lds_barrier();     // final: sreset published by the pose wave
-      // a reset env starts from the template's rates (drone_from_template)
-      if ((sreset >> tid) & 1ull) wx = wy = wz = R(0);
+    };
+    // t = -1 is the part in front of the entry barrier: step 0's rows, by chain a alone
+    for (int t = -1; t < n_steps; ++t) {
+      // behind the barrier of step t-1, the pose wave in step t: the rows of step t+1
+      if (t + 1 < n_steps && (t >= 0 || !from_zero)) {
+        if (from_zero) {
+          wx = wy = wz = R(0);
+          asm volatile("" : "+v"(wx), "+v"(wy), "+v"(wz));
+        } else if (t > 0) {
+          // the rates at the end of step t: chain b's for the lanes reset in step t-1
+          if ((sreset[(t - 1) & 1] >> tid) & 1ull) {
+            const R* e = hbuf + (t & 1) * pstride + cstride + lrow + 5 * nsub;
+            wx = e[0]; wy = e[1]; wz = e[2];
+          }
+        }
+        chain(t + 1, hw + ((t + 1) & 1) * pstride);
+      }
+      lds_barrier();     // the step's barrier: the rows of step t+1 published
     }
     return;
   }
 
   // -------------------------------------------------------------- wave 0: pose
+  action_load<A>(actions_p + slot * slot_stride, nn, nxt);
   Drone<R> s;
   R last[4];
   load_drone(v, nn, s, last, false);
@@ -288,10 +372,12 @@ __global__ __launch_bounds__(3 * kWave) void step_seq_kernel(R* __restrict__ sta
   asm volatile("" : "+v"(s.px), "+v"(s.py), "+v"(s.pz), "+v"(s.qx), "+v"(s.qy), "+v"(s.qz), "+v"(s.qw), "+v"(s.vx),
                "+v"(s.vy), "+v"(s.vz), "+v"(sc), "+v"(head));
   const R wnone[3] = {R(0), R(0), R(0)};
-  auto hand_off = [&](int k, R h[5]) {
+  auto hand_off = [&](const R* hp, int k, R h[5]) {
 #pragma unroll
-    for (int j = 0; j < 5; ++j) h[j] = shand[k & 1][j][tid];
+    for (int j = 0; j < 5; ++j) h[j] = hp[5 * k + j];
   };
+  bool was_reset = false;   // this lane's env was reset in the previous step: its rates are chain b's
+  lds_barrier();            // entry: step 0's rows are there
   for (int t = 0; t < n_steps; ++t) {
     float a[A];
 #pragma unroll
@@ -308,29 +394,33 @@ __global__ __launch_bounds__(3 * kWave) void step_seq_kernel(R* __restrict__ sta
 #pragma unroll
       for (int k = 0; k < 4; ++k) last[k] = rpm[k];   // self.last_clipped_action = clipped_action  :372
     }
+    // the step's rows: the weights of substep k + 1 are read ahead of substep k's arithmetic
+    const R* const hp = hbuf + (t & 1) * pstride + (was_reset ? cstride : 0) + lrow;
+    R h[5];
+    hand_off(hp, 0, h);
     if (nsub > 1) {
-      lds_barrier();   // hand-off 0
-      R h[5];
-      hand_off(0, h);
+      R hn[5];
+      hand_off(hp, 1, hn);
       pose_half<R, false, true>(s, fz, h, wnone, dk);
       for (int k = 1; k < nsub - 1; ++k) {
-        lds_barrier();   // hand-off k
-        hand_off(k, h);
+#pragma unroll
+        for (int j = 0; j < 5; ++j) h[j] = hn[j];
+        hand_off(hp, k + 1, hn);
         pose_half<R, false, false>(s, fz, h, wnone, dk);
       }
+#pragma unroll
+      for (int j = 0; j < 5; ++j) h[j] = hn[j];
     }
     {
-      lds_barrier();   // last hand-off + final rates
-      R h[5];
-      hand_off(nsub - 1, h);
-      s.wx = sw[0][tid]; s.wy = sw[1][tid]; s.wz = sw[2][tid];
+      const R* const e = hp + 5 * nsub;   // the rates after the last substep
+      s.wx = e[0]; s.wy = e[1]; s.wz = e[2];
       const R w[3] = {s.wx, s.wy, s.wz};
-      if (nsub > 1) pose_half<R, true, false>(s, fz, h, w, dk);
+      if (nsub > 1) seq_pose_half_last<R>(s, fz, h, w, dk);
       else pose_half<R, true, true>(s, fz, h, w, dk);
     }
     // final readback (:374) -> obs / reward / done
     R qn[4], Rm[9];
-    if constexpr (kAhead) readback_fused_rare(s.qx, s.qy, s.qz, s.qw, qn, Rm);
+    if constexpr (sizeof(R) == 8) readback_fused_rare(s.qx, s.qy, s.qz, s.qw, qn, Rm);
     else readback_fused(s.qx, s.qy, s.qz, s.qw, qn, Rm);
     AttitudeArgs<R> att = attitude_args(qn);
     bool tilted, up_unused;   // |roll| or |pitch| > 0.4, decided exactly near the limit (attitude_decide)
@@ -384,8 +474,9 @@ __global__ __launch_bounds__(3 * kWave) void step_seq_kernel(R* __restrict__ sta
         for (int k = 0; k < 12; ++k) orow[k] = row12[k];
       }
     }
-    if (tid == 0) { sdone = done_rows; sreset = reset_rows; }
-    lds_barrier();   // final: sdone / sreset published
+    if (tid == 0) { sdone[t & 1] = done_rows; sreset[t & 1] = reset_rows; }
+    was_reset = do_reset;
+    lds_barrier();   // the step's barrier: sdone / sreset published, the next step's rows are there
     // every step leaves its reward and flags; the same lane writes the same address each step, so
     // the last step's values stay.  Nothing waits for these stores before the launch ends.
     if (active) {

@@ -289,7 +289,8 @@ int gpd_step(gpd_sim* sim, const float* actions, float* obs, float* reward,
  * [n_slots][E][D][act_width]; every step writes the same output buffers (as n_steps gpd_step
  * calls would), so they hold the last step's outputs.  No host round trip in between.
  * A sim whose step is the three-wave kernel (single-drone envs, plain DYN, RPM action types, up to
- * 4096 envs; not het) runs n_steps >= 2 as one fused launch per 256 steps: a block keeps its
+ * 4096 envs; not het), in f64, and whose substeps x drones per block fit the fused kernel's LDS
+ * buffers (every default geometry does) runs n_steps >= 2 as one fused launch per 256 steps: a block keeps its
  * drones, counters and action history on chip between the steps, every step still stores its
  * outputs, and the result is bit-identical to n_steps gpd_step calls.  Every other sim gets one
  * kernel launch per step.  The launches have fixed arguments, so the call can be captured in a
