@@ -1475,7 +1475,17 @@ __device__ __forceinline__ void rate_half(R& wx, R& wy, R& wz, const R W[4], con
 // CHECK: the |q|^2 ~ 1 test of dyn_substep (re-normalising a quaternion set from outside).  Only
 // the first substep of a step needs it: from a quaternion with |d - 1| < UnitTol the update
 // M(ω') q/|q| is orthogonal to rounding, so every later substep starts within a few ulp of 1.
-template <typename R, bool ANGV, bool CHECK>
+// FMAX: the x row of the world-frame ang_v by seq_angv_x, for step_seq_kernel's last substep.
+// Left to hipcc, that kernel (no hand-off barrier in front of the call) takes Rm0 wx as the plain
+// product of (Rm0 wx + Rm1 wy) and fuses Rm1 wy, where step_kernel_duo takes Rm1 wy and fuses
+// Rm0 wx: one ulp apart in ang_v x (measured: every other state column had step_kernel_duo's bits).
+template <typename R>
+__device__ __forceinline__ R seq_angv_x(const R Rm[9], const R w[3]) {
+#pragma clang fp contract(off)
+  if constexpr (sizeof(R) == 8) return __builtin_fma(Rm[2], w[2], __builtin_fma(Rm[0], w[0], Rm[1] * w[1]));
+  else return (Rm[0] * w[0] + Rm[1] * w[1]) + Rm[2] * w[2];
+}
+template <typename R, bool ANGV, bool CHECK, bool FMAX = false>
 __device__ __forceinline__ void pose_half(Drone<R>& s, R fz, const R h[5], const R w[3], const DynK<R>& k) {
   R q0[4] = {s.qx, s.qy, s.qz, s.qw};
   R d = q0[0] * q0[0] + q0[1] * q0[1] + q0[2] * q0[2] + q0[3] * q0[3];
@@ -1509,7 +1519,8 @@ __device__ __forceinline__ void pose_half(Drone<R>& s, R fz, const R h[5], const
   s.qz = ((Q * x - P * y) + C * z) + Rr * ww;
   s.qw = ((-P * x - Q * y) - Rr * z) + C * ww;
   if (ANGV) {
-    s.ax = (Rm[0] * w[0] + Rm[1] * w[1]) + Rm[2] * w[2];
+    if (FMAX) s.ax = seq_angv_x(Rm, w);
+    else s.ax = (Rm[0] * w[0] + Rm[1] * w[1]) + Rm[2] * w[2];
     s.ay = (Rm[3] * w[0] + Rm[4] * w[1]) + Rm[5] * w[2];
     s.az = (Rm[6] * w[0] + Rm[7] * w[1]) + Rm[8] * w[2];
   }

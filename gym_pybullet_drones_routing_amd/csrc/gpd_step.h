@@ -33,75 +33,43 @@ __device__ __forceinline__ void tile_copy_out(const float4* tile4, const float* 
   int col = lane - row * NC;
   const int last_row = nact - 1, last_col = NC - 1;
   const int ncs = A == 4 ? 3 : 12;  // state columns
+  using E = std::conditional_t<A == 4, float4, float>;   // a tile element
+  constexpr int EB = sizeof(E);
+  const E* tile = A == 4 ? reinterpret_cast<const E*>(tile4) : reinterpret_cast<const E*>(tilef);
   for (int g0 = lane; g0 - lane < total; g0 += U * NL) {
-    if (A == 4) {
-      float4 val[U];
-      int idx[U];
-      int rr[U], cc[U];
-      bool ok[U];
+    E val[U];
+    int idx[U];
+    int rr[U], cc[U];
+    bool ok[U];
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        ok[u] = g0 + u * NL < total;
-        rr[u] = ok[u] ? row : last_row;
-        cc[u] = ok[u] ? col : last_col;
-        val[u] = tile4[__umul24(cc[u], kPad) + rr[u]];   // 24-bit multiply: full-rate VALU
-        idx[u] = ok[u] ? g0 + u * NL : total - 1;
-        col += dcol; row += drow;
-        if (col >= NC) { col -= NC; ++row; }
-      }
-      GPD_STAMP(8);
-      float4* dst = reinterpret_cast<float4*>(obs) + n0 * NC;
-      if (wt & 1) {
-        // masked-off elements get an offset past num_records: the buffer unit drops the store
-        // (no exec-mask branch per element)
-        const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(dst, 0, total * 16, 0x00020000);
+    for (int u = 0; u < U; ++u) {
+      ok[u] = g0 + u * NL < total;
+      rr[u] = ok[u] ? row : last_row;
+      cc[u] = ok[u] ? col : last_col;
+      val[u] = tile[__umul24(cc[u], kPad) + rr[u]];   // 24-bit multiply: full-rate VALU
+      idx[u] = ok[u] ? g0 + u * NL : total - 1;
+      col += dcol; row += drow;
+      if (col >= NC) { col -= NC; ++row; }
+    }
+    GPD_STAMP(8);
+    E* dst = reinterpret_cast<E*>(obs) + n0 * NC;
+    if (wt & 1) {
+      // masked-off elements get an offset past num_records: the buffer unit drops the store
+      // (no exec-mask branch per element)
+      const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(dst, 0, total * EB, 0x00020000);
 #pragma unroll
-        for (int u = 0; u < U; ++u) store_wt<AUX>(r, ok[u] ? idx[u] * 16 : total * 16, val[u]);
-      } else {
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-          if (ok[u]) dst[idx[u]] = val[u];
-      }
-      GPD_STAMP(9);
-      if (done_rows) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          if (ok[u] && ((done_rows >> rr[u]) & 1ull)) {
-            if (cc[u] >= ncs) reinterpret_cast<float4*>(terminal_obs)[n0 * NC + idx[u]] = val[u];
-          }
-        }
-      }
+      for (int u = 0; u < U; ++u) store_wt<AUX>(r, ok[u] ? idx[u] * EB : total * EB, val[u]);
     } else {
-      float val[U];
-      int idx[U];
-      int rr[U], cc[U];
-      bool ok[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (ok[u]) dst[idx[u]] = val[u];
+    }
+    GPD_STAMP(9);
+    if (done_rows) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        ok[u] = g0 + u * NL < total;
-        rr[u] = ok[u] ? row : last_row;
-        cc[u] = ok[u] ? col : last_col;
-        val[u] = tilef[__umul24(cc[u], kPad) + rr[u]];
-        idx[u] = ok[u] ? g0 + u * NL : total - 1;
-        col += dcol; row += drow;
-        if (col >= NC) { col -= NC; ++row; }
-      }
-      float* dst = obs + n0 * NC;
-      if (wt & 1) {
-        const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(dst, 0, total * 4, 0x00020000);
-#pragma unroll
-        for (int u = 0; u < U; ++u) store_wt<AUX>(r, ok[u] ? idx[u] * 4 : total * 4, val[u]);
-      } else {
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-          if (ok[u]) dst[idx[u]] = val[u];
-      }
-      if (done_rows) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          if (ok[u] && ((done_rows >> rr[u]) & 1ull)) {
-            if (cc[u] >= ncs) terminal_obs[n0 * NC + idx[u]] = val[u];
-          }
+        if (ok[u] && ((done_rows >> rr[u]) & 1ull)) {
+          if (cc[u] >= ncs) reinterpret_cast<E*>(terminal_obs)[n0 * NC + idx[u]] = val[u];
         }
       }
     }

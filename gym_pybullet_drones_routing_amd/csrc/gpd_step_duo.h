@@ -29,6 +29,11 @@ namespace gpd {
 // Of the phases of gpd_step_parts.h the ring append, the terminal-row store and the reset are
 // calls; the action load, the final readback and the tile fill stay written out, for the reason
 // given at step_kernel (gpd_step.h).  The history DMAs and the hover terms are this kernel's own.
+// step_seq_kernel (gpd_step_seq.h) runs the same waves for many steps per launch.  It shares
+// pose_half and the rate pieces; the io wave's mapping, store and terminal passes, the hover hook,
+// the row's state columns, action -> wrench and the look-ahead rate loop are also written there:
+// each was tried as one helper for both kernels and changed this kernel's instructions
+// (profiles/step_seq_shared/README.md).  A fix to one of them goes to gpd_step_seq.h too.
 template <typename R, int ACT, bool IO>
 __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R* __restrict__ state_p,
                                                              const float* __restrict__ actions_p,

@@ -4,7 +4,8 @@
 // replaced with the same types and qualifiers; WHEN a phase runs (the DMA after the first substep,
 // the wait before the ring store, ...) is the calling kernel's schedule and is explained there.
 // step_kernel and step_kernel_duo call only the helpers that leave their machine code as it was
-// and keep the other phases written out (see the note at step_kernel).  So do, for one block
+// and keep the other phases written out (see the note at step_kernel); step_seq_kernel
+// (gpd_step_seq.h) follows step_kernel_duo in this, phase for phase.  So do, for one block
 // each: step_kernel_het (the peeled substep loop: a last-bit change), cmd_rollout_kernel (substep
 // loop and row staging: speed), step_kernel_wide (ring append: registers).  Each says so in place.
 // Needs the layout and loads of gpd_layout.h, the device functions of gpd_device.h and DcHookT

@@ -7,9 +7,13 @@
 // cold caches is paid once per launch instead of once per step.  Every step still stores what an
 // env.step() returns (observation rows, reward, flags, terminal rows), so after the launch memory
 // holds what n_steps launches of step_kernel_duo would have left, bit for bit.
-// The arithmetic of the waves is step_kernel_duo's (gpd_step_duo.h), written out here because
-// lifting it into helpers changes that kernel's instructions: a fix goes to both.
-// Needs step_kernel_duo's helpers (gpd_step_duo.h).
+// The arithmetic of the waves is step_kernel_duo's (gpd_step_duo.h).  The pose halves (pose_half,
+// FMAX for this kernel's last one) and the rate pieces (gpd_device.h) are shared.  The io wave's
+// mapping, store and terminal passes, the hover hook, the row's state columns, action -> wrench and
+// the look-ahead rate loop are written out in both: each was tried as one helper, which changed
+// step_kernel_duo's instructions, and as a helper of this kernel alone, which cost it 0.8 % in the
+// native launch loop (profiles/step_seq_shared/README.md).  A fix to one of them goes to both.
+// Needs what gpd_step_duo.h includes.
 #pragma once
 #include "gpd_step_duo.h"
 
@@ -61,45 +65,6 @@ __host__ __device__ inline int seq_rows(int nsub) { return (5 * nsub + 3) | 1; }
 __host__ __device__ inline int seq_hand_off_at(int tile_bytes) { return (tile_bytes + 15) & ~15; }
 inline size_t seq_lds_bytes(int tile_bytes, int nsub, int tpb, size_t real_bytes) {
   return (size_t)seq_hand_off_at(tile_bytes) + (size_t)2 * 2 * seq_rows(nsub) * tpb * real_bytes;
-}
-
-// The last pose half of a step of nsub > 1 substeps: pose_half<R, true, false> (gpd_device.h)
-// with the x row of the world-frame ang_v spelled out.  Left to hipcc, this kernel (no hand-off
-// barrier in front of the call) takes Rm0 wx as the plain product of (Rm0 wx + Rm1 wy) and fuses
-// Rm1 wy, where step_kernel_duo takes Rm1 wy and fuses Rm0 wx: one ulp apart in ang_v x (measured:
-// every other state column had step_kernel_duo's bits).  The y and z rows and everything else
-// contract as there.  The other lines repeat pose_half's and must stay in step with them.
-template <typename R>
-__device__ __forceinline__ R seq_angv_x(const R Rm[9], const R w[3]) {
-#pragma clang fp contract(off)
-  if constexpr (sizeof(R) == 8) return __builtin_fma(Rm[2], w[2], __builtin_fma(Rm[0], w[0], Rm[1] * w[1]));
-  else return (Rm[0] * w[0] + Rm[1] * w[1]) + Rm[2] * w[2];
-}
-template <typename R>
-__device__ __forceinline__ void seq_pose_half_last(Drone<R>& s, R fz, const R h[5], const R w[3], const DynK<R>& k) {
-  R q0[4] = {s.qx, s.qy, s.qz, s.qw};
-  R d = q0[0] * q0[0] + q0[1] * q0[1] + q0[2] * q0[2] + q0[3] * q0[3];
-  R inv, Rm[9];
-  readback_unit<R, true, false>(q0[0], q0[1], q0[2], q0[3], d, inv, Rm);
-  R Fx = Rm[2] * fz, Fy = Rm[5] * fz, Fz = Rm[8] * fz;
-  Fz = Fz - k.gravity;
-  s.vx = s.vx + k.dt * (Fx * k.inv_m);
-  s.vy = s.vy + k.dt * (Fy * k.inv_m);
-  s.vz = s.vz + k.dt * (Fz * k.inv_m);
-  s.px = s.px + k.dt * s.vx;
-  s.py = s.py + k.dt * s.vy;
-  s.pz = s.pz + k.dt * s.vz;
-  const R shi = h[1] * inv;
-  const R P = h[2] * shi, Q = h[3] * shi, Rr = h[4] * shi;
-  const R C = h[0] * inv;
-  const R x = q0[0], y = q0[1], z = q0[2], ww = q0[3];
-  s.qx = ((C * x + Rr * y) - Q * z) + P * ww;
-  s.qy = ((-Rr * x + C * y) + P * z) + Q * ww;
-  s.qz = ((Q * x - P * y) + C * z) + Rr * ww;
-  s.qw = ((-P * x - Q * y) - Rr * z) + C * ww;
-  s.ax = seq_angv_x(Rm, w);
-  s.ay = (Rm[3] * w[0] + Rm[4] * w[1]) + Rm[5] * w[2];
-  s.az = (Rm[6] * w[0] + Rm[7] * w[1]) + Rm[8] * w[2];
 }
 
 template <typename R, int ACT>
@@ -293,6 +258,8 @@ __global__ __launch_bounds__(4 * kWave) void step_seq_kernel(R* __restrict__ sta
     // step_kernel_duo.  There it hid the recurrence behind a hand-off barrier; here no barrier is
     // left to hide it behind, and the order is kept because it is the text whose contractions give
     // step_kernel_duo's bits (the tests compare them).  Per lane the operations are the same.
+    // (The other copy is step_kernel_duo's kAhead loop; one helper with the publishing step a
+    // functor made its f64 instantiations 4 to 8 bytes shorter.)
     auto chain = [&](int u, R* out) {
       float a[A];
 #pragma unroll
@@ -415,7 +382,7 @@ __global__ __launch_bounds__(4 * kWave) void step_seq_kernel(R* __restrict__ sta
       const R* const e = hp + 5 * nsub;   // the rates after the last substep
       s.wx = e[0]; s.wy = e[1]; s.wz = e[2];
       const R w[3] = {s.wx, s.wy, s.wz};
-      if (nsub > 1) seq_pose_half_last<R>(s, fz, h, w, dk);
+      if (nsub > 1) pose_half<R, true, false, true>(s, fz, h, w, dk);
       else pose_half<R, true, true>(s, fz, h, w, dk);
     }
     // final readback (:374) -> obs / reward / done

@@ -42,7 +42,8 @@ def _assert_twins_equal(a, b, terminal_obs=True):
 
 def _compare(T, P, E=17, act="rpm", lead=0, seed=0, terminal_obs=True, scale=1.0, fused=True, **kw):
     """a: lead + T single steps; b: lead single steps, then step_seq(pool, T).  Then one more single
-    step on both: its history columns are the HBM ring's."""
+    step on both: its history columns are the HBM ring's.  Returns the envs a reset in each of the T
+    steps (terminated or truncated), [T, E]."""
     from gym_pybullet_drones_routing_amd.enums import ActionType
     rng = np.random.default_rng(seed)
     A = 4 if act == "rpm" else 1
@@ -55,15 +56,17 @@ def _compare(T, P, E=17, act="rpm", lead=0, seed=0, terminal_obs=True, scale=1.0
         for k in range(lead):
             a.step(pre[k], terminal_obs=terminal_obs)
             b.step(pre[k], terminal_obs=terminal_obs)
+        done = []
         for t in range(T):
-            a.step(pool[t % P], terminal_obs=terminal_obs)
+            _, _, te, tr = a.step(pool[t % P], terminal_obs=terminal_obs)
+            done.append(te.bool() | tr.bool())
         b.step_seq(pool, T, terminal_obs=terminal_obs)
         _assert_twins_equal(a, b, terminal_obs)
         a.step(pre[0])
         b.step(pre[0])
         torch.cuda.synchronize()
         assert torch.equal(a.obs, b.obs), "next step's obs (HBM ring)"
-        return a.terminated.clone(), a.truncated.clone()
+        return torch.stack(done).cpu()
     finally:
         a.close()
         b.close()
@@ -108,6 +111,21 @@ def test_fused_store_policies_and_full_blocks(tuning):
     """Plain and write-through row / state stores; 64-drone blocks, whose history columns take
     more than one pass of the io wave."""
     _compare(20, 7, E=96, seed=7, tuning=dict(step_waves=3, **tuning))
+
+
+@pytest.mark.parametrize("store_policy", [1, 2], ids=["plain", "write-through"])
+@pytest.mark.parametrize("drones_per_block", [16, 64])
+@pytest.mark.parametrize("act", ["rpm", "one_d_rpm"])
+def test_fused_io_wave_passes(act, drones_per_block, store_policy):
+    """The io wave's store pass and terminal-row pass (csrc/gpd_step_seq.h, wave 2) in each of
+    their forms: float4 and float elements; 16-drone blocks, whose
+    16 * 15 elements fit one pass from registers, and 64-drone blocks, which take several from the
+    tile; plain and write-through rows.  A time limit of one control period and small actions
+    truncate every env in the third of the four steps (test_gpu_step_seq_ahead.py), so every block
+    writes terminal rows inside the launch and runs a step behind the reset."""
+    done = _compare(4, 4, E=96, act=act, seed=14, scale=0.05, episode_len_sec=1 / 30.0,
+                    tuning=dict(step_waves=3, drones_per_block=drones_per_block, store_policy=store_policy))
+    assert done.sum(dim=1).tolist() == [0, 0, 96, 0]
 
 
 def test_fused_long_sequence_crosses_launch_and_time_limit():
