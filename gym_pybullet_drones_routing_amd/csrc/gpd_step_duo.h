@@ -31,9 +31,13 @@ namespace gpd {
 // given at step_kernel (gpd_step.h).  The history DMAs and the hover terms are this kernel's own.
 // step_seq_kernel (gpd_step_seq.h) runs the same waves for many steps per launch.  It shares
 // pose_half and the rate pieces; the io wave's mapping, store and terminal passes, the hover hook,
-// the row's state columns, action -> wrench and the look-ahead rate loop are also written there:
-// each was tried as one helper for both kernels and changed this kernel's instructions
+// action -> wrench and the look-ahead rate loop are also written there: each was tried as one
+// helper for both kernels and changed this kernel's instructions
 // (profiles/step_seq_shared/README.md).  A fix to one of them goes to gpd_step_seq.h too.
+// Two phases differ there on purpose (profiles/step_seq_rows/README.md): the pose wave's action ->
+// thrust (the rate chains publish it) and the row's state columns with reward and flags (the io wave
+// makes and stores them from what the pose wave publishes).  A change to obs_euler_f32 or
+// rate_weights goes to seq_obs_euler_f32 / seq_rate_weights in gpd_step_seq.h too.
 template <typename R, int ACT, bool IO>
 __global__ __launch_bounds__(IO ? 3 * kWave : 2 * kWave) void step_kernel_duo(R* __restrict__ state_p,
                                                              const float* __restrict__ actions_p,

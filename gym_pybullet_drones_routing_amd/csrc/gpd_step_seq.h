@@ -9,10 +9,16 @@
 // holds what n_steps launches of step_kernel_duo would have left, bit for bit.
 // The arithmetic of the waves is step_kernel_duo's (gpd_step_duo.h).  The pose halves (pose_half,
 // FMAX for this kernel's last one) and the rate pieces (gpd_device.h) are shared.  The io wave's
-// mapping, store and terminal passes, the hover hook, the row's state columns, action -> wrench and
-// the look-ahead rate loop are written out in both: each was tried as one helper, which changed
-// step_kernel_duo's instructions, and as a helper of this kernel alone, which cost it 0.8 % in the
-// native launch loop (profiles/step_seq_shared/README.md).  A fix to one of them goes to both.
+// mapping, store and terminal passes, the hover hook, action -> wrench and the look-ahead rate loop
+// are written out in both: each was tried as one helper, which changed step_kernel_duo's
+// instructions, and as a helper of this kernel alone, which cost it 0.8 % in the native launch loop
+// (profiles/step_seq_shared/README.md).  A fix to one of them goes to both.
+// Different from step_kernel_duo on purpose (profiles/step_seq_rows/README.md): there the pose wave
+// turns action into thrust, makes the row's state columns (Euler angles, float conversions, the
+// terminal and the template's row) and stores them with reward and flags; here the rate chains
+// publish the thrust with their rows and the io wave makes and stores the row from what the pose
+// wave publishes (seq_obs_euler_f32 restates obs_euler_f32 on published arguments, seq_rate_weights
+// restates rate_weights with |w|^2 spelled out).  last_clipped_action is formed once, at the end.
 // Needs what gpd_step_duo.h includes.
 #pragma once
 #include "gpd_step_duo.h"
@@ -23,17 +29,26 @@ namespace gpd {
 // Arguments: step_kernel_duo's, with actions_p the base of the action slots [n_slots][N][A];
 // step t of the launch reads slot (slot0 + t) % n_slots.  All of them are fixed per launch (the
 // ring head and the step counters live in device memory), so a hipGraph can replay it.
-//   pose wave  the drone, last_clipped_action, the step counter and the ring head in registers;
-//              per step the substeps' pose halves, the final readback, the task hook, the 12 state
-//              columns of the row, reward and flags, the terminal row and the reset of an env that
-//              finishes; the state, the ring mark and {step_counter, head} once, at the end
-//   rate waves the body rates in registers; the substeps' rate halves of the NEXT step, from the
-//              true rates (chain a) and from the template's zero rates (chain b), see below
+//   pose wave  the drone, the step counter and the ring head in registers; per step the thrust from
+//              the chain it follows, the substeps' pose halves, the final readback, the tilt and
+//              hover decisions and the reset of an env that finishes.  It publishes what the row is
+//              made of (kSeqRowVals reals per lane, 16-byte LDS writes) and four masks: terminal
+//              rows wanted, reset, terminated, truncated.  The state, last_clipped_action (from the
+//              launch's last action row, loaded at entry), the ring mark and {step_counter, head}
+//              once, at the end
+//   rate waves the body rates in registers; the substeps' rate halves and the thrust of the NEXT
+//              step, from the true rates (chain a) and from the template's zero rates (chain b)
 //   io wave   the action history: the ring's slots are DMA'd into the tile once, tile slot s
 //              being ring slot s.  Each step writes its action into slot `head` (and into the HBM
 //              ring, a plain store nothing waits for); history column j of a row is then tile slot
 //              (head + 1 + j) mod L, so an element's LDS address advances by one slot per step
-//              and wraps, while its place in the row stays the same.
+//              and wraps, while its place in the row stays the same.  Behind the barrier of step
+//              t lane i makes row i of step t from the pose wave's entry: the float32 Euler angles
+//              (gimbal branches as a wave-uniform fix-up), the twelve state columns, for a reset
+//              lane the terminal row and then the template's row, reward and flags.  The pose wave
+//              is in step t+1 meanwhile; the row buffer and the masks are double-buffered by step
+//              parity like the hand-off rows.  After the last barrier the io wave finishes the last
+//              row and returns.
 //
 // The rate chain a step ahead.  The body-rate chain of a step needs the step's action and the
 // rates at its start, nothing of the pose (gpd_device.h, above rate_recur), and an open-loop
@@ -58,13 +73,72 @@ namespace gpd {
 // nothing.  Every wave meets n_steps + 1 barriers.
 // Each wave loads its next action row while it works on the current one.
 
-// rows of a lane in one chain's hand-off buffer: 5 weights per substep and the 3 end rates, made
-// odd so that the lanes' rows start in different LDS banks
-__host__ __device__ inline int seq_rows(int nsub) { return (5 * nsub + 3) | 1; }
-// the hand-off buffers' place behind the tile, and the kernel's dynamic LDS
+// rows of a lane in one chain's hand-off buffer: 5 weights per substep, the 3 end rates and the
+// step's thrust fz, made odd so that the lanes' rows start in different LDS banks
+__host__ __device__ inline int seq_rows(int nsub) { return (5 * nsub + 4) | 1; }
+// what the pose wave publishes of a lane's row, in reals: pos(3) vel(3) ang_v(3), getEulerZYX's
+// arguments sarg a b, yaw's two arguments, the readback's x y (the gimbal branches), the reward;
+// one pad, so that a lane's entry is 9 16-byte pairs (f64).  Lanes are 36 dwords apart: 16 lanes'
+// pairs fall into 64 different banks.
+constexpr int kSeqRowVals = 18;
+// the hand-off buffers' place behind the tile, the row buffer [step parity][lane < tpb][kSeqRowVals]
+// behind them (in reals from the hand-off buffers' start), and the kernel's dynamic LDS
 __host__ __device__ inline int seq_hand_off_at(int tile_bytes) { return (tile_bytes + 15) & ~15; }
+__host__ __device__ inline int seq_row_buf_at(int nsub, int tpb) { return 2 * 2 * seq_rows(nsub) * tpb; }
 inline size_t seq_lds_bytes(int tile_bytes, int nsub, int tpb, size_t real_bytes) {
-  return (size_t)seq_hand_off_at(tile_bytes) + (size_t)2 * 2 * seq_rows(nsub) * tpb * real_bytes;
+  return (size_t)seq_hand_off_at(tile_bytes) +
+         ((size_t)seq_row_buf_at(nsub, tpb) + (size_t)2 * kSeqRowVals * tpb) * real_bytes;
+}
+
+// rate_weights (gpd_device.h) with |w|^2 in the very operations of step_kernel_duo's rate wave: wx wx
+// the plain product, wy wy and then wz wz fused onto it.  Left to hipcc the choice of the plain
+// product moves with the code around it; one ulp of |w|^2 shows in cos / sinc at large rotation
+// angles (tests/test_gpu_step_seq_ahead.py::test_large_angle_weights_on_chain_a).  A change to
+// rate_weights goes here too.  f64 only, like the kernel.
+__device__ __forceinline__ double seq_rate_n2(double wx, double wy, double wz) {
+#pragma clang fp contract(off)
+  return __builtin_fma(wz, wz, __builtin_fma(wy, wy, wx * wx));
+}
+// yaw's arguments 2(xy + wz) and ww + xx - yy - zz of obs_euler_f32, in the very operations
+// step_kernel_duo's pose wave compiles them to: xy fused onto the plain product wz, and four plain
+// squares summed in the order written.
+__device__ __forceinline__ void seq_yaw_args(const double q[4], double& yn, double& yd) {
+#pragma clang fp contract(off)
+  const double x = q[0], y = q[1], z = q[2], w = q[3];
+  yn = 2.0 * __builtin_fma(x, y, w * z);
+  yd = ((w * w + x * x) - y * y) - z * z;
+}
+template <typename R>
+__device__ __forceinline__ bool seq_rate_weights(R wx, R wy, R wz, const DynK<R>& k, R h[5], R& n2) {
+  n2 = seq_rate_n2(wx, wy, wz);
+  const bool rot = n2 > R(1e-16);
+  const R t2 = n2 * k.hdt2;
+  R co, sc;
+  cos_sinc(t2, co, sc);
+  h[0] = co; h[1] = k.hdt * sc;
+  h[2] = rot ? wx : R(0); h[3] = rot ? wy : R(0); h[4] = rot ? wz : R(0);
+  return t2 >= R(0.25);
+}
+
+// obs_euler_f32 (gpd_device.h) from the published arguments: sarg a b as attitude_decide left them,
+// yn = 2(xy + wz) and yd = ww + xx - yy - zz formed by the pose wave (another wave's contraction of
+// them could differ in the last bit), x y of the readback for the gimbal branches.  The gimbal
+// flag is attitude_args' / attitude_literal's predicate of sarg.
+template <typename R>
+__device__ __forceinline__ void seq_obs_euler_f32(R sarg, R a, R b, R yn, R yd, R x, R y, float& roll, float& pitch,
+                                                  float& yaw) {
+  const bool gimbal = sarg <= R(-0.99999) || sarg >= R(0.99999);
+  const R sa = sarg < R(-1) ? R(-1) : (sarg > R(1) ? R(1) : sarg);
+  pitch = asinf((float)sa);
+  roll = atan2f((float)a, (float)b);
+  yaw = atan2f((float)yn, (float)yd);
+  if (GPD_RARE(__ballot(gimbal) != 0ull)) {
+    if (sarg <= R(-0.99999)) {
+      pitch = -1.57079632679489661923f; roll = 0.0f; yaw = (float)(R(2) * g_atan2(x, -y));
+    } else if (sarg >= R(0.99999)) {
+      pitch = 1.57079632679489661923f; roll = 0.0f; yaw = (float)(R(2) * g_atan2(-x, y));
+    }
+  }
 }
 
 template <typename R, int ACT>
@@ -74,12 +148,15 @@ __global__ __launch_bounds__(4 * kWave) void step_seq_kernel(R* __restrict__ sta
                                                              StepIO<R> io, int n_slots, int slot0, int n_steps,
                                                              int hand_off_at) {
   static_assert(!act_is_pid(ACT), "the fused sequence kernel serves the RPM action types");
+  static_assert(sizeof(R) == 8, "the fused sequence kernel is built for f64 sims only (gpd.hip, step_seq_fn)");
   v.state = state_p; v.ctr = ctr_p; v.npad = npad_p; v.N = n_p; v.tpb = tpb_p;
   constexpr int A = act_width(ACT);
   extern __shared__ float4 tile4[];
   float* tilef = reinterpret_cast<float*>(tile4);
   __shared__ unsigned long long sdone[2];    // rows whose terminal observation is wanted (tile rows), by step parity
   __shared__ unsigned long long sreset[2];   // lanes whose env was reset in the step, by step parity
+  __shared__ unsigned long long sterm[2];    // lanes whose env is `terminated` / `truncated` in the step,
+  __shared__ unsigned long long strunc[2];   // by step parity (the io wave stores the flags)
   __shared__ int shead[kWave];               // ring head of every lane's env at entry (io wave)
   const Consts<R>& c = *cp;
   const int tid = threadIdx.x & (kWave - 1);
@@ -102,6 +179,11 @@ __global__ __launch_bounds__(4 * kWave) void step_seq_kernel(R* __restrict__ sta
   const int pstride = 2 * cstride;         // even step -> odd step
   const bool own = tid < v.tpb;
   const int lrow = (own ? tid : 0) * rows;
+  // the row buffer [parity][lane][kSeqRowVals], as 16-byte pairs
+  typedef R R2 __attribute__((ext_vector_type(2)));
+  constexpr int kRowPairs = kSeqRowVals / 2;
+  R2* const rbuf = reinterpret_cast<R2*>(hbuf + seq_row_buf_at(c.nsub, v.tpb)) + (own ? tid : 0) * kRowPairs;
+  const int rpar = v.tpb * kRowPairs;      // even step -> odd step
 
   if (wave == 2) {
     // ------------------------------------------------------------ wave 2: history columns
@@ -150,6 +232,8 @@ __global__ __launch_bounds__(4 * kWave) void step_seq_kernel(R* __restrict__ sta
       off[u] = ok ? (i * NC + c0 + k) * EB : nrec;
       idx[u] = s * kPad + i;
     }
+    float tmpl12[12];                             // the template's row, for the lanes reset in a step
+    row12_from_template(c.init0, tmpl12);
     int tmod = 0;                                 // steps of this launch so far, mod L
     asm volatile("s_barrier" ::: "memory");       // entry (this wave publishes nothing to the others there)
     for (int t = 0; t < n_steps; ++t) {
@@ -225,6 +309,47 @@ __global__ __launch_bounds__(4 * kWave) void step_seq_kernel(R* __restrict__ sta
           }
         }
       }
+      // the step's row: state columns from what the pose wave published, reward and flags.  Lane
+      // i makes row i in every step, so the last step's values stay.  Nothing waits for these
+      // stores before the launch ends.
+      {
+        const unsigned long long rs = sreset[t & 1], tm = sterm[t & 1], tr = strunc[t & 1];
+        if (active) {
+          const R2* const rp = rbuf + (t & 1) * rpar;
+          R2 e[kRowPairs];
+#pragma unroll
+          for (int k = 0; k < kRowPairs; ++k) e[k] = rp[k];
+          float roll, pitch, yaw;
+          seq_obs_euler_f32<R>(e[4].y, e[5].x, e[5].y, e[6].x, e[6].y, e[7].x, e[7].y, roll, pitch, yaw);
+          float row12[12] = {(float)e[0].x, (float)e[0].y, (float)e[1].x, roll, pitch, yaw,
+                             (float)e[1].y, (float)e[2].x, (float)e[2].y, (float)e[3].x, (float)e[3].y, (float)e[4].x};
+          const float reward = v.task != TASK_NONE ? (float)e[8].x : -1.0f;
+          if ((rs >> tid) & 1ull) {
+            if ((dr >> tid) & 1ull) row12_store<A>(io.terminal_obs + n * v.W, row12);
+#pragma unroll
+            for (int k = 0; k < 12; ++k) row12[k] = tmpl12[k];
+          }
+          if (A == 4) {
+            const float4 r0 = make_float4(row12[0], row12[1], row12[2], row12[3]);
+            const float4 r1 = make_float4(row12[4], row12[5], row12[6], row12[7]);
+            const float4 r2 = make_float4(row12[8], row12[9], row12[10], row12[11]);
+            if (wt_rows) {
+              const int o = tid * v.W * 4;
+              store_wt(rsrc, o, r0); store_wt(rsrc, o + 16, r1); store_wt(rsrc, o + 32, r2);
+            } else {
+              float4* o4 = reinterpret_cast<float4*>(io.obs + n * v.W);
+              o4[0] = r0; o4[1] = r1; o4[2] = r2;
+            }
+          } else {
+            float* orow = io.obs + n * v.W;
+#pragma unroll
+            for (int k = 0; k < 12; ++k) orow[k] = row12[k];
+          }
+          io.reward[n] = reward;
+          io.term[n] = (uint8_t)((tm >> tid) & 1ull);
+          io.trunc[n] = (uint8_t)((tr >> tid) & 1ull);
+        }
+      }
       // one slot on: the head, every element's tile index, the step count mod L
       hd = hd + 1 == L ? 0 : hd + 1;
       tmod = tmod + 1 == L ? 0 : tmod + 1;
@@ -270,11 +395,12 @@ __global__ __launch_bounds__(4 * kWave) void step_seq_kernel(R* __restrict__ sta
 #pragma unroll
       for (int k = 0; k < 4; ++k) rpm[k] = (R)action_to_rpm(dk.hover_f32, a[A == 4 ? k : 0]);
       rpm_wrench<R, 0>(rpm, dk, c, W);
+      if (own) out[5 * nsub + 3] = W[0];   // the step's thrust, for the pose wave
       rate_recur(wx, wy, wz, W, dk);   // ω_1
       for (int k = 0; k < nsub - 1; ++k) {
         R h[5], n2;
         const R cx = wx, cy = wy, cz = wz;   // ω_{k+1}
-        const bool big = rate_weights(cx, cy, cz, dk, h, n2);
+        const bool big = seq_rate_weights(cx, cy, cz, dk, h, n2);
         rate_weights_big(big, n2, dk, h);
         if (own) {
 #pragma unroll
@@ -284,7 +410,7 @@ __global__ __launch_bounds__(4 * kWave) void step_seq_kernel(R* __restrict__ sta
       }
       {
         R h[5], n2;
-        const bool big = rate_weights(wx, wy, wz, dk, h, n2);
+        const bool big = seq_rate_weights(wx, wy, wz, dk, h, n2);
         rate_weights_big(big, n2, dk, h);
         if (own) {
           R* const o = out + 5 * (nsub - 1);
@@ -316,7 +442,9 @@ __global__ __launch_bounds__(4 * kWave) void step_seq_kernel(R* __restrict__ sta
   }
 
   // -------------------------------------------------------------- wave 0: pose
-  action_load<A>(actions_p + slot * slot_stride, nn, nxt);
+  // the launch's last action row: last_clipped_action is needed for the state store alone
+  float alast[A];
+  action_load<A>(actions_p + ((slot0 + n_steps - 1) % n_slots) * slot_stride, nn, alast);
   Drone<R> s;
   R last[4];
   load_drone(v, nn, s, last, false);
@@ -329,15 +457,14 @@ __global__ __launch_bounds__(4 * kWave) void step_seq_kernel(R* __restrict__ sta
   // where the lane's results go, formed once (global-address-space pointers, as step_kernel_duo)
   gpd_global R* st_out = (gpd_global R*)(v.state + tidx(nn, 0, kStateComps));
   int st_off = (int)(tidx(nn, 0, kStateComps) * sizeof(R));
-  gpd_global float* rew_out = (gpd_global float*)(io.reward + nn);
-  gpd_global uint8_t* term_out = (gpd_global uint8_t*)(io.term + nn);
-  gpd_global uint8_t* trunc_out = (gpd_global uint8_t*)(io.trunc + nn);
   gpd_global gpd_v2i* ctr_out = (gpd_global gpd_v2i*)(v.ctr + nn);
-  asm volatile("" : "+v"(st_out), "+v"(st_off), "+v"(rew_out), "+v"(term_out), "+v"(trunc_out), "+v"(ctr_out));
+  asm volatile("" : "+v"(st_out), "+v"(st_off), "+v"(ctr_out));
   // the entry loads have landed before the first step: a wait for them left inside the loop would,
   // from the second step on, wait for the previous step's stores
   asm volatile("" : "+v"(s.px), "+v"(s.py), "+v"(s.pz), "+v"(s.qx), "+v"(s.qy), "+v"(s.qz), "+v"(s.qw), "+v"(s.vx),
                "+v"(s.vy), "+v"(s.vz), "+v"(sc), "+v"(head));
+#pragma unroll
+  for (int j = 0; j < A; ++j) asm volatile("" : "+v"(alast[j]));
   const R wnone[3] = {R(0), R(0), R(0)};
   auto hand_off = [&](const R* hp, int k, R h[5]) {
 #pragma unroll
@@ -346,23 +473,10 @@ __global__ __launch_bounds__(4 * kWave) void step_seq_kernel(R* __restrict__ sta
   bool was_reset = false;   // this lane's env was reset in the previous step: its rates are chain b's
   lds_barrier();            // entry: step 0's rows are there
   for (int t = 0; t < n_steps; ++t) {
-    float a[A];
-#pragma unroll
-    for (int j = 0; j < A; ++j) a[j] = nxt[j];
-    next_slot();
-    if (t + 1 < n_steps) action_load<A>(actions_p + slot * slot_stride, nn, nxt);
-    R fz;
-    {
-      R rpm[4], W[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) rpm[k] = (R)action_to_rpm(dk.hover_f32, a[A == 4 ? k : 0]);
-      rpm_wrench<R, 0>(rpm, dk, c, W);
-      fz = W[0];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) last[k] = rpm[k];   // self.last_clipped_action = clipped_action  :372
-    }
     // the step's rows: the weights of substep k + 1 are read ahead of substep k's arithmetic
     const R* const hp = hbuf + (t & 1) * pstride + (was_reset ? cstride : 0) + lrow;
+    // rpm_wrench's W[0] of the step's action, by the chain the lane follows
+    const R fz = hp[5 * nsub + 3];
     R h[5];
     hand_off(hp, 0, h);
     if (nsub > 1) {
@@ -392,9 +506,7 @@ __global__ __launch_bounds__(4 * kWave) void step_seq_kernel(R* __restrict__ sta
     AttitudeArgs<R> att = attitude_args(qn);
     bool tilted, up_unused;   // |roll| or |pitch| > 0.4, decided exactly near the limit (attitude_decide)
     attitude_decide<R, true, false>(s.qx, s.qy, s.qz, s.qw, att, tilted, up_unused);
-    float roll, pitch, yaw;
-    obs_euler_f32(qn, att, roll, pitch, yaw);
-    float reward = -1.0f;
+    R rew = R(0);   // the reward in f64; the io wave rounds it (and stores -1 without a task)
     bool term = false, trunc = false;
     if (v.task != TASK_NONE) {
       const R tx = tk.tg[0] - s.px, ty = tk.tg[1] - s.py, tz = tk.tg[2] - s.pz;
@@ -402,7 +514,7 @@ __global__ __launch_bounds__(4 * kWave) void step_seq_kernel(R* __restrict__ sta
       R r = R(2) - d2 * d2;
       r = r > R(0) ? r : R(0);
       const bool oob = g_abs(s.px) > tk.bound_xy || g_abs(s.py) > tk.bound_xy || s.pz > R(2) || tilted;
-      reward = (float)r;
+      rew = r;
       // np.linalg.norm(...) < .0001 (HoverAviary.py:92) with the root taken only inside the band
       // where it decides (step_kernel_duo)
       term = d2 < R(0.99e-8);
@@ -412,49 +524,31 @@ __global__ __launch_bounds__(4 * kWave) void step_seq_kernel(R* __restrict__ sta
     }
     const bool done = term || trunc;
     const bool do_reset = done && v.autoreset;
-    float row12[12] = {(float)s.px, (float)s.py, (float)s.pz, roll, pitch, yaw,
-                       (float)s.vx, (float)s.vy, (float)s.vz, (float)s.ax, (float)s.ay, (float)s.az};
-    if (do_reset) {
-      if (active && io.terminal_obs != nullptr) row12_store<A>(io.terminal_obs + n * v.W, row12);
-      reset_to_template(tk.ini, s, last, row12);
+    // what the step's row is made of, for the io wave (kSeqRowVals): the live values, before a reset
+    R yn, yd;
+    seq_yaw_args(qn, yn, yd);
+    if (own) {
+      R2* const rp = rbuf + (t & 1) * rpar;
+      rp[0] = R2{s.px, s.py}; rp[1] = R2{s.pz, s.vx}; rp[2] = R2{s.vy, s.vz};
+      rp[3] = R2{s.ax, s.ay}; rp[4] = R2{s.az, att.sarg}; rp[5] = R2{att.a, att.b};
+      rp[6] = R2{yn, yd};
+      rp[7] = R2{qn[0], qn[1]}; rp[8] = R2{rew, R(0)};
     }
+    if (do_reset) drone_from_template(tk.ini, s);
     const unsigned long long done_rows = __ballot(do_reset && active && io.terminal_obs != nullptr);
     const unsigned long long reset_rows = __ballot(do_reset);
-    // the row's 12 state columns straight from registers; the io wave writes the rest
-    if (active) {
-      if (A == 4) {
-        const float4 r0 = make_float4(row12[0], row12[1], row12[2], row12[3]);
-        const float4 r1 = make_float4(row12[4], row12[5], row12[6], row12[7]);
-        const float4 r2 = make_float4(row12[8], row12[9], row12[10], row12[11]);
-        if (v.wt & 1) {
-          const __amdgpu_buffer_rsrc_t r =
-              __builtin_amdgcn_make_buffer_rsrc(io.obs + n0 * v.W, 0, nact * v.W * 4, 0x00020000);
-          const int o = tid * v.W * 4;
-          store_wt(r, o, r0); store_wt(r, o + 16, r1); store_wt(r, o + 32, r2);
-        } else {
-          float4* o4 = reinterpret_cast<float4*>(io.obs + n * v.W);
-          o4[0] = r0; o4[1] = r1; o4[2] = r2;
-        }
-      } else {
-        float* orow = io.obs + n * v.W;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) orow[k] = row12[k];
-      }
-    }
+    const unsigned long long term_rows = __ballot(term), trunc_rows = __ballot(trunc);
+    if (tid == 0) { sterm[t & 1] = term_rows; strunc[t & 1] = trunc_rows; }
     if (tid == 0) { sdone[t & 1] = done_rows; sreset[t & 1] = reset_rows; }
     was_reset = do_reset;
-    lds_barrier();   // the step's barrier: sdone / sreset published, the next step's rows are there
-    // every step leaves its reward and flags; the same lane writes the same address each step, so
-    // the last step's values stay.  Nothing waits for these stores before the launch ends.
-    if (active) {
-      *rew_out = reward;
-      *term_out = (uint8_t)(term ? 1 : 0);
-      *trunc_out = (uint8_t)(trunc ? 1 : 0);
-    }
+    lds_barrier();   // the step's barrier: the masks and the row published, the next step's rows are there
     sc = do_reset ? 0 : sc + nsub;
     head = head + 1 == v.ring_len ? 0 : head + 1;
   }
   if (!active) return;
+  // self.last_clipped_action = clipped_action (:372) of the last step; zero in a lane reset in it
+#pragma unroll
+  for (int k = 0; k < 4; ++k) last[k] = was_reset ? R(0) : (R)action_to_rpm(dk.hover_f32, alast[A == 4 ? k : 0]);
   store_drone_step_at<R, kAuxWt>(v, st_out, st_off, s, last);
   mark_last_in_ring_single(v, n);
   *ctr_out = gpd_v2i{sc, head};
